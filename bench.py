@@ -7,12 +7,18 @@ fused point kernel on its contiguous shard of the Vecchia ordering (inputs resid
 sums are all-reduced over RCCL (N > 1), and the value is delivered to the host (as an optimiser would need it).
 Model creation (ordering + device neighbour search) is set-up and reported separately, as in BASELINE.md.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (vecchia_point_kernel, MODE_NLL): its
-average duration is measured live with HIP events on the stream it is launched on (gpb_hip_vecchia_bench);
-`cpu_baseline` (rank 0, N = 1 only) times the unmodified reference (oracle/_ref, kind "reference") -- or the C
-restatement (kind "port") when oracle/_ref is absent -- on a bounded sample on this box's host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line; `roofline` is for the dominant kernel (vecchia_point_kernel, MODE_NLL): its average duration is measured with HIP
+events around every launch inside the timed loop.
+--full adds everything else the line reports next to the metric: the same call through the Python wrapper and the
+batched entry point, a separate loop of kernel launches, the A/B of the sums through ncclAllReduce (N > 1), the other
+BASELINE configurations (N = 1; --no-extras skips them) and `cpu_baseline` (N = 1; --no-cpu-baseline skips it), which
+times the unmodified reference (oracle/_ref, kind "reference") -- or the C restatement (kind "port") when oracle/_ref
+is absent -- on a bounded sample on the host cores.
+--dump-outputs DIR writes what the timed call returned in the last timed step (the negative log-likelihood, float64)
+as DIR/negll.npy; the inputs are fixed by seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -234,8 +240,10 @@ def main():
     ap.add_argument("--m", type=int, default=30)
     ap.add_argument("--d", type=int, default=2)
     ap.add_argument("--cov", default="exponential", choices=["exponential", "matern_1.5", "matern_2.5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the metric's line: skip the other configurations' measurements reported next to it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the sustained rate")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other configurations' measurements reported next to the metric")
+    ap.add_argument("--full", action="store_true", help="also run every measurement reported next to the metric (off: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result as DIR/<name>.npy")
     # (the self-launcher below hands the ranks their arguments through GPB_BENCH_ARGV: torch.distributed.run's own parser would reject an
     #  abbreviation-ambiguous script option such as --n before it ever reaches the script)
     argv = json.loads(os.environ["GPB_BENCH_ARGV"]) if (len(sys.argv) == 1 and "GPB_BENCH_ARGV" in os.environ) else sys.argv[1:]
@@ -474,10 +482,14 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    # what the caller of the timed path received in the last timed step (every rank gets the job's value; rank 0 writes it)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "negll.npy"), np.array([last], dtype=np.float64))
     # the same call through the package-style wrapper (GPModel.neg_log_likelihood: argument checks + numpy marshalling per call), untimed
     # steps first so that both loops run at the same clocks; reported in config, never as `value`
     wrapper_ms = None
-    if not distributed or native:
+    if args.full and (not distributed or native):
         for k in range(5):
             mdl.neg_log_likelihood(cov_pars_of(k))
         sync()
@@ -490,7 +502,7 @@ def main():
     # A/B inside the same run (real multi-device launches only): the same timed call with the sums through ncclAllReduce (+ publish kernel) instead of
     # the mailbox -- north_star names "RCCL all-reduce of log-likelihood scalars"; both rates are in the line, `value` is the mailbox's (the default)
     ab_rccl = None
-    if distributed and native_rccl and use_mailbox and os.environ.get("GPB_BENCH_NO_AB", "0") != "1":
+    if args.full and distributed and native_rccl and use_mailbox and os.environ.get("GPB_BENCH_NO_AB", "0") != "1":
         mbox_name_ranks = st.mailbox_info()[1]
         st.mailbox_detach()
         try:
@@ -516,7 +528,7 @@ def main():
     # batched entry point (GPB_HIP_EvalNegLogLikelihoodBatch): K parameter sets per call, ONE synchronisation and ONE all-reduce of 3 K
     # doubles -- what an optimiser's line search / a grid of trial points would use; reported next to the metric, never as `value`
     batched = None
-    if not distributed or native:
+    if args.full and (not distributed or native):
         Kb = 32
         cps = np.stack([cov_pars_of(k) for k in range(Kb)])
         mdl.neg_log_likelihood_batch(cps)
@@ -533,10 +545,15 @@ def main():
         batched = {"K": Kb, "evals_per_s": 4 * Kb / dtb, "ms_per_eval": dtb / (4 * Kb) * 1e3,
                    "call": "GPB_HIP_EvalNegLogLikelihoodBatch: one synchronisation and one all-reduce per K evaluations"}
 
-    # dominant kernel, measured with HIP events on its own stream (this rank's shard)
-    ms_total, ms_kernel_sep, _ = st.bench(shim.MODE_NLL, ct, var0, a0, 1, max(3, min(args.steps, 20)))      # a separate loop of launches (cross-check)
-    ms_gtotal, ms_gkernel, _ = st.bench(shim.MODE_GRAD, ct, var0, a0, 1, 3)
-    ms_kernel = ms_kernel_inloop if (timed_launches >= args.steps and ms_kernel_inloop > 0) else ms_kernel_sep
+    # dominant kernel, measured with HIP events on its own stream (this rank's shard); the separate loop of launches is the cross-check
+    # (--full) and the fall-back when the in-loop events did not cover the timed steps
+    in_loop = timed_launches >= args.steps and ms_kernel_inloop > 0
+    ms_kernel_sep = ms_gkernel = None
+    if args.full or not in_loop:
+        ms_total, ms_kernel_sep, _ = st.bench(shim.MODE_NLL, ct, var0, a0, 1, max(3, min(args.steps, 20)))
+    if args.full:
+        ms_gtotal, ms_gkernel, _ = st.bench(shim.MODE_GRAD, ct, var0, a0, 1, 3)
+    ms_kernel = ms_kernel_inloop if in_loop else ms_kernel_sep
     npts = i1 - i0
     bytes_launch = npts * algorithmic_bytes_per_point(m, d)
     flops_launch = npts * algorithmic_flops_per_point(m, d, ct)
@@ -584,14 +601,16 @@ def main():
                        "shard_points_per_gpu": npts, "parallelism": "points sharded x%d, sum of 3 fp64 over the ranks (%s)" % (world, ("node-local shared-memory mailbox, %d ranks (RCCL up with %d ranks for the big messages)" % (mailbox_ranks, rccl_ranks)) if use_mailbox else ("in-library RCCL, %d ranks" % rccl_ranks if native_rccl else ("torch.distributed nccl" if distributed else "single GPU"))) + (" -- REHEARSAL on one device" if rehearsal else ""),
                        "rccl_ranks": rccl_ranks, "mailbox_ranks": mailbox_ranks, "prewarm_evals": PREWARM, "rehearsal": rehearsal, "per_rank": per_rank, "ab_sums_through_ncclAllReduce": ab_rccl,
                        "process_group": ("gloo (rehearsal bootstrap)" if rehearsal else "nccl (RCCL)") if distributed else None,
-                       "kernel_ms_source": "HIP events around every point-kernel launch INSIDE the timed loop (%d launches); separate loop of launches: %.4f ms" % (timed_launches, ms_kernel_sep),
+                       "kernel_ms_source": "HIP events around every point-kernel launch INSIDE the timed loop (%d launches)" % timed_launches +
+                                           ("; separate loop of launches: %.4f ms" % ms_kernel_sep if ms_kernel_sep is not None else ""),
                        "setup_s_model_creation_incl_device_neighbor_search": round(t_setup, 3),
                        "last_negll": last, "batched": batched,
                        # what one evaluation costs outside the point kernel (launch, the in-kernel final sums, pinned-memory hand-over, the
                        # all-reduce for N > 1, the foreign call): ms_per_step - kernel_ms, both measured in this run
                        "overhead_us": round((dt / args.steps * 1e3 - ms_kernel) * 1e3, 2),
                        "ms_per_step_through_python_wrapper": wrapper_ms,
-                       "grad_eval_ms_kernel": round(ms_gkernel, 4), "grad_over_nll_kernel_time": round(ms_gkernel / ms_kernel, 3)},
+                       "grad_eval_ms_kernel": round(ms_gkernel, 4) if ms_gkernel is not None else None,
+                       "grad_over_nll_kernel_time": round(ms_gkernel / ms_kernel, 3) if ms_gkernel is not None else None},
             # BASELINE.json's metric asks for "% HBM roofline": the primary object is the HBM view of the dominant kernel (algorithmic gather
             # bytes of SURVEY.md 8d / HIP-event kernel time / 8 TB/s).  The kernel is NOT HBM-bound -- it is bound by fp64 VALU issue
             # (DESIGN.md 4.1); that view is `roofline_fp64_valu` (no MFMA is issued; vector fp64 peak 78.6 TFLOP/s).
@@ -606,7 +625,7 @@ def main():
                                    "algorithmic_flops_per_launch": flops_launch,
                                    "note": "exp / sqrt / division counted as ONE flop each (SURVEY.md 8d); instruction mix: profiles/r04_point_kernel_instruction_mix.txt"},
         }
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # the one HBM-bound kernel of the path: dense covariance assembly (exact GP), measured live
             try:
                 ne = 16384
@@ -648,7 +667,7 @@ def main():
                 ex1.close()
             except Exception as e:
                 out["config1_exact_gp_n2000"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # LightGBM feature-histogram build at a size where GB/s means something (8d: n = 1e7 rows, F = 50,
             # 255 bins, constant hessian): algorithmic bytes = rows * (F + 8 + 4) in + F * bins * 16 out
             try:
@@ -730,7 +749,7 @@ def main():
                     out["config4_vecchia_laplace"][kk]["time_source"] = "host timer of the phase / iteration count (all kernels of an iteration + launch gaps); per-kernel figures from kernel durations: roofline_kernels_from_trace"
             except Exception as e:
                 out["config4_vecchia_laplace"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # full-scale Vecchia / VIF: one likelihood evaluation at n = 1e5, m = 30, 200 inducing points
             try:
                 nv = 100000
@@ -786,7 +805,7 @@ def main():
                 del mq
             except Exception as e:
                 out["vif_non_gaussian"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # the direct caller of the hot path: a complete maximum-likelihood fit of (sigma2, sigma1_2, rho) on the
             # bench model -- y uploaded once, 3 / 7 doubles back per evaluation.  y = smooth signal + noise so that the optimum is interior.
             try:
@@ -803,7 +822,7 @@ def main():
                     "negll": mdl.get_current_neg_log_likelihood()}
             except Exception as e:
                 out["fit_covariance_parameters"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # BASELINE config 3: the device work of one GPBoost iteration (Gaussian likelihood, Vecchia m = 30, n = 1e5; tree of 31 leaves
             # on F = 50 features x 255 bins), every step through the C ABI with host arrays in and out (scripts/gpu_boost_iter.py)
             try:
@@ -886,7 +905,7 @@ def main():
                     out["config3_boosting_iteration"]["route_b"] = {"error": "%s: %s" % (type(e).__name__, e)}
             except Exception as e:
                 out["config3_boosting_iteration"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # shard_sweep (VERDICT r05 #1 iv / #11): each of the 8 shards an 8-rank job evaluates (parallel.shard_range), run ALONE on this one device -- point-kernel
             # time by HIP events and the wall time of one synchronous evaluation of the shard (launch + in-launch sums + pinned-memory hand-over).  A ONE-DEVICE
             # PROJECTION of the per-rank work of an N = 8 launch (later shards do the same arithmetic on a different gather footprint), never a scaling number.
@@ -926,7 +945,7 @@ def main():
                     del m5
             except Exception as e:
                 out["shard_sweep"] = dict(out.get("shard_sweep", {}), error="%s: %s" % (type(e).__name__, e))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # (1) the reference's CPU path on the host cores with the GPU IDLE (round 3 timed it beside a loop that drove the GPU flat out)
             try:
                 out["cpu_baseline"] = cpu_baseline(coords, y, cov_function, shape, m, cov_pars, n)

@@ -31,11 +31,11 @@ for STEP in "$@"; do
     bench)     NAME=${REST%%:*}; ARGS=${REST#*:}; [ "$NAME" = "$REST" ] && ARGS=""
                timeout 900 python bench.py $ARGS > $O/bench_$NAME.json 2> $O/bench_$NAME.err; echo "rc=$?"; cut -c1-1500 $O/bench_$NAME.json; show $O/bench_$NAME.err 4 ;;
     rehearsal) for N in ${REST//,/ }; do
-                 timeout 900 python bench.py --gpus $N --steps 20 --warmup 5 > $O/bench_rehearsal_N$N.json 2> $O/bench_rehearsal_N$N.err; echo "N=$N rc=$?"
+                 timeout 900 python bench.py --gpus $N --steps 20 --warmup 5 --full > $O/bench_rehearsal_N$N.json 2> $O/bench_rehearsal_N$N.err; echo "N=$N rc=$?"
                  cut -c1-900 $O/bench_rehearsal_N$N.json; grep -v "^$" $O/bench_rehearsal_N$N.err | grep -iv "warn\|OMP_NUM\|\*\*\*" | tail -4 | cut -c1-300
                done ;;
     dist1)     # the multi-GPU code path with ONE rank under the driver's launcher: nccl process group, in-library RCCL communicator, mailbox, the A/B of the sums through ncclAllReduce
-               GPB_BENCH_FORCE_DIST=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_forced_dist_1rank.json 2> $O/bench_forced_dist_1rank.err
+               GPB_BENCH_FORCE_DIST=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/bench_forced_dist_1rank.json 2> $O/bench_forced_dist_1rank.err
                echo "rc=$?"; cut -c1-1500 $O/bench_forced_dist_1rank.json; grep -v "^$" $O/bench_forced_dist_1rank.err | grep -iv "warn\|OMP_NUM\|\*\*\*" | tail -4 | cut -c1-300 ;;
     config5)   timeout 900 python bench.py --n 1000000 --m 40 --d 3 --cov matern_2.5 --no-cpu-baseline --no-extras --steps 20 --warmup 5 > $O/bench_config5.json 2> $O/bench_config5.err
                echo "rc=$?"; cut -c1-1800 $O/bench_config5.json; show $O/bench_config5.err 4 ;;
