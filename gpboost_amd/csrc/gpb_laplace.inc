@@ -589,6 +589,8 @@ int gpb_hip_vecchia_laplace_set_preconditioner(gpb_hip_vecchia_t* h, int type, i
   LaplaceState* s = h->lap;
   const int rk = rank > 0 ? rank : (type == 2 ? 200 : 50);            // default_fitc_preconditioner_rank_ / default_piv_chol_preconditioner_rank_ (re_model_template.h:5921-5922)
   if (type == 1 && rk > h->n) return fail("'fitc_piv_chol_preconditioner_rank' cannot be larger than the dimension of the mode (= number of unique locations) ");   // likelihoods.h:936-938
+  if (type == 1 && rk > gpb::pc_max_rank)
+    return fail("pivoted_cholesky preconditioner: at most %d columns on this path (the k x 4 operand of a probe chunk is kept in 64 KB of LDS; got fitc_piv_chol_preconditioner_rank = %d)", gpb::pc_max_rank, rk);
   if (s->pc_type != type || s->pc_rank != rk) { s->grad_state = false; s->gvec_state = false; }
   if (s->pc_type != type) {
     // "fitc" and "pivoted_cholesky" share d_pcL / d_pcM / d_pcG but each owns further work arrays: with the same rank k a handle that ran one of them would
@@ -622,6 +624,58 @@ int gpb_hip_vecchia_laplace_set_inducing_points(gpb_hip_vecchia_t* h, int32_t k,
 }
 
 }  // extern "C"
+
+// Test entry (include/gpb_hip.h): one of the block operations of the low-rank preconditioners on host data, sized and called as pc_refresh / pc_apply do it.
+// Every input lies between two runs of NaN on the device and the scratch starts as NaN: a value read from beyond an operand, or a partial sum that was never written,
+// shows in the result.  `out` travels to the device whole (guard + result + guard doubles) and comes back whole.
+int gpb_hip_lowrank_ops_check(int32_t op, int32_t n, int32_t k, int32_t ncol, int32_t nc, int32_t mode, const double* L, const double* W, const double* M, const double* X,
+                              const double* x2, int32_t in_place, int32_t guard, double* out) {
+  API_BEGIN();
+  if (check_device()) return -1;
+  if (op < 0 || op > 2 || n < 1 || k < 1 || k > gpb::pc_max_rank || ncol < 1 || (nc != 1 && nc != 4) || mode < 0 || mode > 4 || guard < 0 || !L || !W || !out)
+    return fail("gpb_hip_lowrank_ops_check: invalid argument (op 0..2, n, k (<= %d), ncol >= 1, nc 1 or 4, mode 0..4)", gpb::pc_max_rank);
+  if ((op == 1 && (!M || !X)) || (op == 2 && (!x2 || (!X && !in_place)))) return fail("gpb_hip_lowrank_ops_check: null operand");
+  constexpr size_t PAD = 64;
+  std::vector<double*> bufs;
+  const auto free_tmp = scope_exit([&] { for (double* b : bufs) (void)hipFree(b); });
+  std::vector<double> stage;
+  const auto upload = [&](const double* src, size_t cnt, double** dev) -> hipError_t {      // NaN | src | NaN
+    stage.assign(cnt + 2 * PAD, std::nan(""));
+    std::memcpy(stage.data() + PAD, src, sizeof(double) * cnt);
+    double* d = nullptr;
+    hipError_t e = hipMalloc(&d, sizeof(double) * stage.size());
+    if (e != hipSuccess) return e;
+    bufs.push_back(d);
+    *dev = d + PAD;
+    return hipMemcpy(d, stage.data(), sizeof(double) * stage.size(), hipMemcpyHostToDevice);
+  };
+  const int parts = gpb::pc_parts(n);
+  const size_t nblk = (size_t)ncol * n * nc, nx2 = (size_t)ncol * k * nc, npairs = (size_t)k * (k + 1) / 2;
+  const size_t nout = op == 0 ? npairs : (op == 1 ? nx2 : nblk);
+  const size_t npart = std::max((size_t)ncol * parts * k * nc, (size_t)parts * npairs);      // (pc_apply)
+  double *d_L = nullptr, *d_W = nullptr, *d_M = nullptr, *d_X = nullptr, *d_x2 = nullptr, *d_part = nullptr, *d_out = nullptr;
+  HIP_OK(upload(L, (size_t)n * k, &d_L));
+  HIP_OK(upload(W, (size_t)n, &d_W));
+  if (op == 1) HIP_OK(upload(M, (size_t)k * k, &d_M));
+  if (op == 1 || (op == 2 && !in_place)) HIP_OK(upload(X, nblk, &d_X));
+  if (op == 2) HIP_OK(upload(x2, nx2, &d_x2));
+  HIP_OK(hipMalloc(&d_out, sizeof(double) * (nout + 2 * (size_t)guard)));
+  bufs.push_back(d_out);
+  HIP_OK(hipMemcpy(d_out, out, sizeof(double) * (nout + 2 * (size_t)guard), hipMemcpyHostToDevice));
+  if (op != 2) {
+    stage.assign(npart, std::nan(""));
+    HIP_OK(hipMalloc(&d_part, sizeof(double) * npart));
+    bufs.push_back(d_part);
+    HIP_OK(hipMemcpy(d_part, stage.data(), sizeof(double) * npart, hipMemcpyHostToDevice));
+  }
+  double* res = d_out + guard;
+  if (op == 0) HIP_OK(gpb::pc_gram(d_L, d_W, n, k, d_part, res, nullptr));
+  else if (op == 1) HIP_OK(gpb::pc_ltwx(d_L, d_W, d_M, d_X, n, k, ncol, nc, d_part, res, nullptr));
+  else HIP_OK(gpb::pc_combine(d_L, d_W, in_place ? res : d_X, d_x2, n, k, ncol, nc, mode, res, nullptr));
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(out, d_out, sizeof(double) * (nout + 2 * (size_t)guard), hipMemcpyDeviceToHost));
+  API_END();
+}
 
 namespace {
 enum : int { LAP_RESET_MODE = 1, LAP_KEEP_GRAD_STATE = 2 };

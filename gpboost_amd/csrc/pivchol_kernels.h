@@ -9,6 +9,7 @@ namespace gpb {
 // Layouts.  L: the rank-k factor [n][k] row-major, row = STORAGE slot of the point (the order of the Laplace vectors).  Block vectors:
 // [chunk][row][nc] (nc = 1: one plain column per chunk; 4: the probe block).  Small operands: [chunk][k][nc].
 int pc_parts(int n);                         // row slices of the tall-skinny reductions
+constexpr int pc_max_rank = 2048;            // columns of L the block kernels take: the small operand of a chunk, k x 4 doubles, lives in the 64 KB of LDS of a launch (pc_ltwx refuses more)
 // pivoted Cholesky of the NON-approximated covariance var * k(a * dist) (PivotedCholsekyFactorizationSigma): one argmax + one update launch per column
 hipError_t pc_piv_init(int n, int k, double var, double* L, double* diag, int* pi, int* pos, int* done, hipStream_t st);
 // out2 = { point chosen at step m (as a double), sum |diag| over the points not yet chosen }; swaps pi / pos as the reference does

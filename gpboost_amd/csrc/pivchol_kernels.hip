@@ -291,22 +291,38 @@ __global__ __launch_bounds__(256, 2) void pc_ltwx_mfma_kernel(const double* __re
   }
 }
 // x2[chunk][q][c] = sum_p M[q][p] y[p][c],  y = the slices' partial sums: four quarters of the slices added in slice order each (by four thread groups -- the sum over 256
-// slices was a chain of 256 dependent loads per element, 77 us for 200 elements), then the quarters in order
-template <int NC>
+// slices was a chain of 256 dependent loads per element, 77 us for 200 elements), then the quarters in order.
+// QLDS: the quarter sums pass through LDS (k * NC * 40 bytes with y); !QLDS: one thread adds the four quarters of its element one after the other and keeps them in
+// registers (k * NC * 8 bytes: the ranks whose 40 bytes per element pass the 64 KB of a launch) -- the same additions in the same order, bit for bit.
+template <int NC, bool QLDS>
 __global__ __launch_bounds__(1024) void pc_small_kernel(const double* __restrict__ part, int parts, const double* __restrict__ M, int k, double* __restrict__ x2) {
-  extern __shared__ double s_y[];                      // k * NC, then 4 x k * NC quarter sums
+  extern __shared__ double s_y[];                      // k * NC, then (QLDS) 4 x k * NC quarter sums
   const int chunk = blockIdx.x;
   const int len = k * NC;
-  double* s_q = s_y + len;
-  const int sub = threadIdx.x >> 8, tl = threadIdx.x & 255;
-  const int b0 = (int)((long long)parts * sub / 4), b1 = (int)((long long)parts * (sub + 1) / 4);
-  for (int e = tl; e < len; e += 256) {
-    double acc = 0.0;
-    for (int b = b0; b < b1; ++b) acc += part[((size_t)chunk * parts + b) * len + e];
-    s_q[sub * len + e] = acc;
+  if (QLDS) {
+    double* s_q = s_y + len;
+    const int sub = threadIdx.x >> 8, tl = threadIdx.x & 255;
+    const int b0 = (int)((long long)parts * sub / 4), b1 = (int)((long long)parts * (sub + 1) / 4);
+    for (int e = tl; e < len; e += 256) {
+      double acc = 0.0;
+      for (int b = b0; b < b1; ++b) acc += part[((size_t)chunk * parts + b) * len + e];
+      s_q[sub * len + e] = acc;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < len; e += 1024) s_y[e] = ((s_q[e] + s_q[len + e]) + s_q[2 * len + e]) + s_q[3 * len + e];
+  } else {
+    for (int e = threadIdx.x; e < len; e += 1024) {
+      double q4[4];
+#pragma unroll
+      for (int sub = 0; sub < 4; ++sub) {
+        const int b0 = (int)((long long)parts * sub / 4), b1 = (int)((long long)parts * (sub + 1) / 4);
+        double acc = 0.0;
+        for (int b = b0; b < b1; ++b) acc += part[((size_t)chunk * parts + b) * len + e];
+        q4[sub] = acc;
+      }
+      s_y[e] = ((q4[0] + q4[1]) + q4[2]) + q4[3];
+    }
   }
-  __syncthreads();
-  for (int e = threadIdx.x; e < len; e += 1024) s_y[e] = ((s_q[e] + s_q[len + e]) + s_q[2 * len + e]) + s_q[3 * len + e];
   __syncthreads();
   for (int e = threadIdx.x; e < len; e += 1024) {
     const int q = e / NC, c = e % NC;
@@ -658,7 +674,10 @@ hipError_t pc_gram(const double* L, const double* W, int n, int k, double* part,
 }
 hipError_t pc_ltwx(const double* L, const double* W, const double* M, const double* X, int n, int k, int ncol, int nc, double* part, double* x2, hipStream_t st) {
   const int parts = pc_parts(n);
-  const size_t lds = sizeof(double) * (size_t)k * nc * 5;
+  if (k < 1 || (nc != 1 && nc != 4) || (size_t)k * nc > (size_t)pc_max_rank * 4) return hipErrorInvalidValue;      // (the small operand of a chunk in 64 KB of LDS)
+  const size_t len = (size_t)k * nc;
+  const bool qlds = sizeof(double) * len * 5 <= 65536;      // the quarter sums beside y in the 64 KB of LDS a launch gets without asking for more (nc = 4: k <= 409)
+  const size_t lds = sizeof(double) * len * (qlds ? 5 : 1);
   if (nc == 4) {
     if (ncol > 8) {      // groups of 16 chunks (64 block-vector columns), one launch each: the pointers move, the kernel sees chunks 0 .. 15 of its group
       for (int g0 = 0; g0 < ncol; g0 += 16)
@@ -667,10 +686,12 @@ hipError_t pc_ltwx(const double* L, const double* W, const double* M, const doub
     }
     else if (ncol > 4) hipLaunchKernelGGL(pc_ltwx_mfma_kernel<2>, dim3(parts, 1), dim3(256), 0, st, L, W, X, n, k, ncol, part);
     else hipLaunchKernelGGL(pc_ltwx_mfma_kernel<1>, dim3(parts, 1), dim3(256), 0, st, L, W, X, n, k, ncol, part);
-    hipLaunchKernelGGL(pc_small_kernel<4>, dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
+    if (qlds) hipLaunchKernelGGL((pc_small_kernel<4, true>), dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
+    else hipLaunchKernelGGL((pc_small_kernel<4, false>), dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
   } else {
     hipLaunchKernelGGL(pc_ltwx_kernel<1>, dim3(parts, ncol), dim3(512), 0, st, L, W, X, n, k, part);
-    hipLaunchKernelGGL(pc_small_kernel<1>, dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
+    if (qlds) hipLaunchKernelGGL((pc_small_kernel<1, true>), dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
+    else hipLaunchKernelGGL((pc_small_kernel<1, false>), dim3(ncol), dim3(1024), lds, st, part, parts, M, k, x2);
   }
   return hipGetLastError();
 }

@@ -433,6 +433,28 @@ class LocalGroup(object):
         return res
 
 
+def lowrank_ops_check(op, L, W, ncol=1, nc=4, M=None, X=None, x2=None, mode=0, in_place=False, guard=64, sentinel=-7.25e300):
+    """One block operation of the low-rank preconditioners on the device (gpb_hip_lowrank_ops_check; layouts: csrc/pivchol_kernels.h).  op "gram": L' diag(W) L, packed
+    lower triangle; "ltwx": M (L' (W .* X)) -> (ncol, k, nc); "combine": modes 0..4 on X (ncol, n, nc) and x2 (ncol, k, nc) -> (ncol, n, nc), in_place: out == X on the device.
+    -> (result, guards_intact): the result lies between two runs of `guard` sentinels on the device; guards_intact tells that both came back unchanged."""
+    L = np.ascontiguousarray(L, dtype=np.float64); W = np.ascontiguousarray(W, dtype=np.float64)
+    n, k = L.shape
+    opi = {"gram": 0, "ltwx": 1, "combine": 2}[op]
+    shape = (k * (k + 1) // 2,) if opi == 0 else ((ncol, k, nc) if opi == 1 else (ncol, n, nc))
+    size = int(np.prod(shape))
+    Mc = None if M is None else np.ascontiguousarray(M, dtype=np.float64)
+    Xc = None if X is None else np.ascontiguousarray(X, dtype=np.float64)
+    x2c = None if x2 is None else np.ascontiguousarray(x2, dtype=np.float64)
+    assert W.shape == (n,) and (Mc is None or Mc.shape == (k, k)) and (Xc is None or Xc.shape == (ncol, n, nc)) and (x2c is None or x2c.shape == (ncol, k, nc))
+    out = np.full(size + 2 * guard, sentinel)
+    if opi == 2 and in_place:
+        out[guard:guard + size] = Xc.ravel()
+    _shim_call(_lib().gpb_hip_lowrank_ops_check(C.c_int(opi), C.c_int(n), C.c_int(k), C.c_int(ncol), C.c_int(nc), C.c_int(mode), _p(L), _p(W), _p(Mc), _p(Xc), _p(x2c),
+                                                C.c_int(1 if in_place else 0), C.c_int(guard), _p(out)))
+    intact = bool(np.all(out[:guard] == sentinel) and np.all(out[guard + size:] == sentinel))
+    return out[guard:guard + size].reshape(shape).copy(), intact
+
+
 def mailbox_create(world):
     """rank 0: create the node-local mailbox segment for `world` ranks -> its name (bytes; hand it to every rank's mailbox_attach)"""
     buf = C.create_string_buffer(64)

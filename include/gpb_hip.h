@@ -66,6 +66,16 @@ GPB_HIP_EXPORT int gpb_hip_dev_free(void* p);
 GPB_HIP_EXPORT int gpb_hip_dev_to_host(void* dst_host, const void* src_dev, uint64_t bytes);
 /* Runs the fp64-DPP primitives against their compiler-scheduled equivalents on the device. */
 GPB_HIP_EXPORT int gpb_hip_selftest(void);
+/* Test entry: ONE block operation of the low-rank preconditioners ("pivoted_cholesky" / "fitc" / full-scale Vecchia) on host data, sized and launched as the model path
+ * does it, the result copied back.  L [n][k] row-major, W [n], block vectors X / result [ncol chunks][n][nc] (nc = 1 or 4), small operands [ncol][k][nc]:
+ *   op 0  G = L' diag(W) L, lower triangle packed by rows (k (k + 1) / 2)
+ *   op 1  x2 = M (L' (W .* X)),  M [k][k] row-major (ncol * k * nc)
+ *   op 2  mode 0: W .* (X - L x2), 1: X - L x2, 2: L x2 + X ./ sqrt(W), 3: -W .* (L x2), 4: X + W .* (L x2) (ncol * n * nc); in_place != 0: X is the result's own
+ *         buffer (taken from `out`, the argument X is not read)
+ * out: guard + result + guard doubles; the whole buffer goes to the device before the operation and comes back after it, so a caller that fills the guards
+ * with a sentinel sees any store outside the result. */
+GPB_HIP_EXPORT int gpb_hip_lowrank_ops_check(int32_t op, int32_t n, int32_t k, int32_t ncol, int32_t nc, int32_t mode, const double* L, const double* W, const double* M,
+                                             const double* X, const double* x2, int32_t in_place, int32_t guard, double* out);
 
 /* ------------------------------------------------------------------------------------
  * Vecchia state: replaces what CreateREComponentsVecchia builds on the host

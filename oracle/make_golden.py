@@ -173,6 +173,24 @@ def laplace_pivchol_fixture(out_dir, only=()):
     np.savez_compressed(os.path.join(out_dir, "laplace_pivchol_ref.npz"), **res)
 
 
+def laplace_pivchol_probes_fixture(out_dir):
+    """cases.LAPLACE_PIVCHOL_PROBE_CASES: the low-rank preconditioners with num_rand_vec_trace > 50 -- value and gradient from the reference's own CalcGradPars at
+    cases.LAPLACE_TIGHT: <key>_negll_direct, <key>_grad_direct."""
+    res = {}
+    tight = dict(cg_delta_conv=cases.LAPLACE_TIGHT["cg_delta_conv"], delta_conv_mode_finding=cases.LAPLACE_TIGHT["delta_conv_mode_finding"])
+    for key, (name, t) in cases.LAPLACE_PIVCHOL_PROBE_CASES.items():
+        pc = cases.LAPLACE_PIVCHOL_CASES[name]
+        c = cases.LAPLACE_CASES[pc["model"]]
+        coords, y = cases.make_pivchol_data(pc)
+        cp = np.asarray(c["cov_pars"][0], dtype=np.float64)
+        nll, g, _ = refdrv.ref_laplace_nll_grad(coords, y, cp, pc["lik"], None, c["cov_function"], c["shape"], c["m"], c["ordering"], c["seed"], **tight,
+                                                cg_preconditioner_type=pc.get("pc", "pivoted_cholesky"), piv_chol_rank=-999 if pc["rank"] is None else int(pc["rank"]),
+                                                num_rand_vec_trace=t)
+        res[key + "_negll_direct"] = np.float64(nll); res[key + "_grad_direct"] = g
+        print("low-rank preconditioner, %d probes (CalcGradPars, tight)" % t, key, "%.12f" % nll, g, flush=True)
+    np.savez_compressed(os.path.join(out_dir, "laplace_pivchol_probes_ref.npz"), **res)
+
+
 def laplace_aux_fixture(out_dir, only=()):
     """gamma and negative_binomial Vecchia-Laplace models (auxiliary shape parameter estimated with the covariance parameters): the reference's own
       *_negll_0                      GPB_EvalNegLogLikelihood at (cov_pars, aux) with the default thresholds
@@ -1567,6 +1585,8 @@ if __name__ == "__main__":
         laplace_aux_gd_fixture(os.path.join(ROOT, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "laplace_vresp":
         laplace_vresp_fixture(os.path.join(ROOT, "tests", "golden"))
+    elif len(sys.argv) > 1 and sys.argv[1] == "laplace_pivchol_probes":
+        laplace_pivchol_probes_fixture(os.path.join(ROOT, "tests", "golden"))
     elif len(sys.argv) > 1 and sys.argv[1] == "laplace_pivchol":
         laplace_pivchol_fixture(os.path.join(ROOT, "tests", "golden"), sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "laplace_aux":

@@ -536,6 +536,14 @@ class sample_weights(object):
         return False
 
 
+def _check_probes(rc):
+    """Return code -3 of the Vecchia-Laplace entries: more probe vectors asked for than the preconditioner context inside which the call runs has columns of
+    rand_vec_trace_I2_ / rand_vec_trace_P_ / rand_vec_trace_I3_ (its num_rand_vec) -- the C side refuses instead of reading past the buffer."""
+    if rc == -3:
+        raise ValueError("more probe vectors than the preconditioner context was built with: give the context the same num_rand_vec (and seed_rand) as the evaluation")
+    return rc
+
+
 _PROBE_RUN_ID = 0      # cg_generator_counter_ at the time rand_vec_trace_I_ is drawn: 0, or 1 when rand_vec_trace_I2_ was drawn first (pivoted_cholesky)
 
 
@@ -566,8 +574,8 @@ class pivoted_cholesky_preconditioner(object):
     def __enter__(self):
         global _PROBE_RUN_ID
         fn = lib().orc_set_pivchol
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        fn(self.L.ctypes.data, self.L.shape[1], self.rv2.ctypes.data)
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        fn(self.L.ctypes.data, self.L.shape[1], self.rv2.ctypes.data, self.rv2.shape[1])
         _PROBE_RUN_ID = 1
         return self
 
@@ -601,8 +609,8 @@ class fitc_preconditioner(object):
     def __enter__(self):
         global _PROBE_RUN_ID
         fn = lib().orc_set_fitc
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p]
-        fn(self.C.ctypes.data, self.V.ctypes.data, self.Sm.ctypes.data, float(self.logdet_Sm), self.k, self.rv2.ctypes.data)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
+        fn(self.C.ctypes.data, self.V.ctypes.data, self.Sm.ctypes.data, float(self.logdet_Sm), self.k, self.rv2.ctypes.data, self.rv2.shape[1])
         _PROBE_RUN_ID = 1
         return self
 
@@ -677,10 +685,10 @@ def vecchia_laplace_logit(coords, nn, cov_type, var, a, y01, num_rand_vec=50, se
     out = np.empty(6); mode = np.empty(n)
     fe = None if fixed_effects is None else np.ascontiguousarray(fixed_effects, dtype=np.float64)
     with _aux_context(link, aux, yd, None):
-      rc = lib().orc_vecchia_laplace_binary_fe(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(nn, C.c_int), C.c_int(n), C.c_int(m),
+      rc = _check_probes(lib().orc_vecchia_laplace_binary_fe(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(nn, C.c_int), C.c_int(n), C.c_int(m),
                                           _p(yi, C.c_int), None if fe is None else _p(fe, C.c_double), _p(rv, C.c_double), C.c_int(rv.shape[1]), C.c_int(cg_max_num_it),
                                           C.c_int(cg_max_num_it_tridiag), C.c_double(cg_delta_conv), C.c_double(delta_conv_mode),
-                                          _p(out, C.c_double), _p(mode, C.c_double))
+                                          _p(out, C.c_double), _p(mode, C.c_double)))
     return -out[0], dict(rc=rc, newton_it=int(out[1]), cg_it=int(out[2]), log_det=out[3], lanczos_it=int(out[4]),
                          mll_no_det=out[5], mode=mode, A=A, D=D)
 
@@ -740,18 +748,18 @@ def vecchia_laplace_dup(coords_u, nn, cov_type, var, a, unique_idx, y, num_rand_
     if grad:
         A, D, Ag, Dg, bad = vecchia_factor(coords_u, nn, cov_type, var, a, gauss=False, grad=True)
         g = np.empty(2)
-        rc = lib().orc_vecchia_laplace_grad_map(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int),
+        rc = _check_probes(lib().orc_vecchia_laplace_grad_map(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int),
                                                 C.c_int(n), C.c_int(m), _p(dptr, C.c_int), _p(yi, C.c_int), None if fe is None else _p(fe, C.c_double), _p(rv, C.c_double),
                                                 C.c_int(rv.shape[1]), C.c_int(cg_max_num_it), C.c_int(cg_max_num_it_tridiag), C.c_double(cg_delta_conv),
-                                                C.c_double(delta_conv_mode), _p(out, C.c_double), _p(g, C.c_double), _p(mode, C.c_double), C.c_int(0))
+                                                C.c_double(delta_conv_mode), _p(out, C.c_double), _p(g, C.c_double), _p(mode, C.c_double), C.c_int(0)))
         if rc != 0:
             raise RuntimeError("orc_vecchia_laplace_grad_map failed")
         return -out[0], g, mode
     A, D, bad = vecchia_factor(coords_u, nn, cov_type, var, a, gauss=False)
-    rc = lib().orc_vecchia_laplace_binary_fe_map(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(nn, C.c_int), C.c_int(n), C.c_int(m), _p(dptr, C.c_int),
+    rc = _check_probes(lib().orc_vecchia_laplace_binary_fe_map(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(nn, C.c_int), C.c_int(n), C.c_int(m), _p(dptr, C.c_int),
                                                  _p(yi, C.c_int), None if fe is None else _p(fe, C.c_double), _p(rv, C.c_double), C.c_int(rv.shape[1]),
                                                  C.c_int(cg_max_num_it), C.c_int(cg_max_num_it_tridiag), C.c_double(cg_delta_conv), C.c_double(delta_conv_mode),
-                                                 _p(out, C.c_double), _p(mode, C.c_double))
+                                                 _p(out, C.c_double), _p(mode, C.c_double)))
     return -out[0], dict(rc=rc, newton_it=int(out[1]), cg_it=int(out[2]), log_det=out[3], lanczos_it=int(out[4]), mll_no_det=out[5], mode=mode)
 
 
@@ -773,11 +781,11 @@ def vecchia_laplace_grad(coords, nn, cov_type, var, a, y01, num_rand_vec=50, see
     mode = np.zeros(n) if mode_init is None else np.ascontiguousarray(mode_init, dtype=np.float64).copy()
     dbg = np.zeros(2 * n + 8) if want_parts else None
     with _aux_context(link, aux, yd, aux_g4):
-        rc = lib().orc_vecchia_laplace_grad(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double),
+        rc = _check_probes(lib().orc_vecchia_laplace_grad(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double),
                                             _p(nn, C.c_int), C.c_int(n), C.c_int(m), _p(yi, C.c_int), None if fe is None else _p(fe, C.c_double),
                                             _p(rv, C.c_double), C.c_int(rv.shape[1]), C.c_int(cg_max_num_it), C.c_int(cg_max_num_it_tridiag),
                                             C.c_double(cg_delta_conv), C.c_double(delta_conv_mode), _p(out, C.c_double), _p(g, C.c_double),
-                                            _p(mode, C.c_double), C.c_int(0 if mode_init is None else 1), None if dbg is None else _p(dbg, C.c_double))
+                                            _p(mode, C.c_double), C.c_int(0 if mode_init is None else 1), None if dbg is None else _p(dbg, C.c_double)))
     if rc != 0:
         raise RuntimeError("orc_vecchia_laplace_grad failed")
     if link == 6:      # t: d(-mll) / d (log scale, log df)
@@ -969,11 +977,11 @@ def vecchia_laplace_dup_grad_F(coords_u, nn, cov_type, var, a, unique_idx, y, li
     rv = gen_rand_normal(n, num_rand_vec, seed_rand, _PROBE_RUN_ID)
     A, D, Ag, Dg, bad = vecchia_factor(coords_u, nn, cov_type, var, a, gauss=False, grad=True)
     out = np.empty(6); g = np.empty(2); mode = np.zeros(n); dbg = np.zeros(2 * n + 8)
-    rc = lib().orc_vecchia_laplace_grad_map_dbg(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int),
+    rc = _check_probes(lib().orc_vecchia_laplace_grad_map_dbg(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int),
                                                 C.c_int(n), C.c_int(m), _p(dptr, C.c_int), _p(yi, C.c_int), None if fe is None else _p(fe, C.c_double),
                                                 _p(rv, C.c_double), C.c_int(rv.shape[1]), C.c_int(cg_max_num_it), C.c_int(cg_max_num_it_tridiag),
                                                 C.c_double(cg_delta_conv), C.c_double(delta_conv_mode), _p(out, C.c_double), _p(g, C.c_double),
-                                                _p(mode, C.c_double), C.c_int(0), _p(dbg, C.c_double))
+                                                _p(mode, C.c_double), C.c_int(0), _p(dbg, C.c_double)))
     if rc != 0:
         raise RuntimeError("orc_vecchia_laplace_grad_map_dbg failed")
     dld, sv = dbg[:n], dbg[n:2 * n]
@@ -1138,9 +1146,9 @@ class vif_laplace(object):
         _PROBE_RUN_ID = 0
         f = self.factor
         fn = lib().orc_set_vif
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         fn(f["C"].ctypes.data, f["V"].ctypes.data, f["Sm"].ctypes.data, float(f["logdet_Sm"]), self.k, self.pc,
-           None if self.rvP is None else self.rvP.ctypes.data, None if self.rv3 is None else self.rv3.ctypes.data)
+           None if self.rvP is None else self.rvP.ctypes.data, None if self.rv3 is None else self.rv3.ctypes.data, 0 if self.rvP is None else self.rvP.shape[1])
         return self
 
     def __exit__(self, *exc):
@@ -1337,10 +1345,10 @@ def vif_laplace_grad(co, nn, ip, ip_pc, cov_type, var, a, y, likelihood="bernoul
         lib().orc_vif_set_parts_out.argtypes = [C.c_void_p]
         lib().orc_vif_set_parts_out(parts.ctypes.data)
         with _aux_context(link, aux, yd, aux_g4):
-            rc = lib().orc_vecchia_laplace_grad(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int), C.c_int(n),
+            rc = _check_probes(lib().orc_vecchia_laplace_grad(C.c_int(link), _p(A, C.c_double), _p(D, C.c_double), _p(Ag, C.c_double), _p(Dg, C.c_double), _p(nn, C.c_int), C.c_int(n),
                                                 C.c_int(m), _p(yi, C.c_int), None, _p(rv, C.c_double), C.c_int(t), C.c_int(cg_max_num_it), C.c_int(cg_max_num_it_tridiag),
                                                 C.c_double(cg_delta_conv), C.c_double(delta_conv_mode), _p(out, C.c_double), _p(g, C.c_double), _p(mode, C.c_double),
-                                                C.c_int(0 if mode_init is None else 1), None)
+                                                C.c_int(0 if mode_init is None else 1), None))
         lib().orc_vif_set_parts_out(None)
     if rc != 0:
         raise RuntimeError("orc_vecchia_laplace_grad failed")

@@ -221,6 +221,18 @@ LAPLACE_PIVCHOL_CASES = {
     "fitc_gamma_u3d_n1200_r60": dict(model="lap_u3d_n1200_mat25_m15", lik="gamma", rank=60, aux=0.8, true_aux=1.2, pc="fitc"),
 }
 
+# More than 50 probe vectors (num_rand_vec_trace of GPB_SetOptimConfig) on LAPLACE_PIVCHOL_CASES: key -> (case, num_rand_vec_trace).  With more than 16 chunks of 4 probes
+# (t > 64) the block kernels of the low-rank part launch once per group of 16 chunks.  Value and gradient from the reference's own CalcGradPars at LAPLACE_TIGHT:
+# tests/golden/laplace_pivchol_probes_ref.npz (oracle/make_golden.py laplace_pivchol_probes), keys <key>_negll_direct / <key>_grad_direct.
+LAPLACE_PIVCHOL_PROBE_CASES = {
+    "pc_logit_n2000_t52": ("pc_logit_n2000", 52),
+    "pc_logit_n2000_t64": ("pc_logit_n2000", 64),
+    "pc_logit_n2000_t100": ("pc_logit_n2000", 100),
+    "pc_poisson_n1500_r20_t68": ("pc_poisson_n1500_r20", 68),
+    "fitc_logit_n1500_r100_t52": ("fitc_logit_n1500_r100", 52),
+    "fitc_logit_n1500_r100_t68": ("fitc_logit_n1500_r100", 68),
+}
+
 
 # cg_preconditioner_type = "vecchia_response" (round 6; the fifth entry of SUPPORTED_PRECONDITIONERS_NONGAUSS_VECCHIA_, re_model_template.h:5906): the (W^-1 + Sigma) form of
 # the solves preconditioned with the Vecchia approximation of W^-1 + Sigma itself (likelihoods.h:16315-16323, :16439-16450, :16471-16473).  EVALUATION ONLY -- the reference

@@ -33,10 +33,10 @@ void orc_set_weights(const double* w);
 void orc_set_binomial(int on);
 void orc_clear_aux(void);
 int orc_pivoted_cholesky(const double* coords, int n, int d, int cov_type, double var, double a, int max_it, double err_tol, double* L_out);
-void orc_set_pivchol(const double* L_k, int k, const double* rand_vec2);
+void orc_set_pivchol(const double* L_k, int k, const double* rand_vec2, int rand_vec2_cols);
 void orc_clear_pivchol(void);
 void orc_set_vecchia_response(const double* coords, int d, int cov_type, double var, double a);
-void orc_set_fitc(const double* C_nk, const double* V_nk, const double* Sm_kk, double logdet_Sm, int k, const double* rand_vec2);
+void orc_set_fitc(const double* C_nk, const double* V_nk, const double* Sm_kk, double logdet_Sm, int k, const double* rand_vec2, int rand_vec2_cols);
 int orc_vecchia_laplace_grad_map_dbg(int link, const double* A, const double* D, const double* Ag, const double* Dg, const int* nn, int n, int m,
                                      const int* dptr, const int* y_int, const double* fe, const double* rand_vec, int t, int cg_max_num_it,
                                      int cg_max_num_it_tridiag, double cg_delta_conv, double delta_conv_mode_finding, double* out6, double* grad2,
@@ -295,7 +295,7 @@ int laplace_run(gpb_hip_vecchia* h, int cov, double var, double a, int nrv, int 
       }
     }
     orc_gen_rand_normal(seed, 0ull, k, nrv, rv2.data());
-    orc_set_fitc(pcL.data(), pcV.data(), pcSm.data(), 2. * ld, k, rv2.data());
+    orc_set_fitc(pcL.data(), pcV.data(), pcSm.data(), 2. * ld, k, rv2.data(), nrv);
   } else
   if (h->pc_type == 3) orc_set_vecchia_response(h->coords.data(), h->d, cov, var, a);      // vecchia_response: no low-rank part, no second set of normals
   else
@@ -304,7 +304,7 @@ int laplace_run(gpb_hip_vecchia* h, int cov, double var, double a, int nrv, int 
     pcL.assign((size_t)n * k, 0.); rv2.assign((size_t)k * nrv, 0.);
     orc_pivoted_cholesky(h->coords.data(), n, h->d, cov, var, a, k, 1e-6, pcL.data());
     orc_gen_rand_normal(seed, 0ull, k, nrv, rv2.data());
-    orc_set_pivchol(pcL.data(), k, rv2.data());
+    orc_set_pivchol(pcL.data(), k, rv2.data(), nrv);
   }
   orc_gen_rand_normal(seed, (pc && h->pc_type != 3) ? 1ull : 0ull, n, nrv, rv.data());
   std::vector<int> dptr;
@@ -341,6 +341,8 @@ EXPORT const char* gpb_hip_get_last_error(void) { return g_err; }
 EXPORT int gpb_hip_device_count(int* count) { if (count) *count = 1; return 0; }
 EXPORT int gpb_hip_set_device(int) { return 0; }
 EXPORT int gpb_hip_selftest(void) { return 0; }
+EXPORT int gpb_hip_lowrank_ops_check(int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, const double*, const double*, const double*, const double*, const double*, int32_t,
+                                     int32_t, double*) { return fail("mock: the block operations of the low-rank preconditioners need the device library"); }
 EXPORT int gpb_hip_pinned_alloc(size_t bytes, void** out) { *out = std::malloc(bytes ? bytes : 1); return *out ? 0 : fail("mock: out of memory"); }
 EXPORT int gpb_hip_pinned_free(void* p) { std::free(p); return 0; }
 EXPORT int gpb_hip_vecchia_comm_info(gpb_hip_vecchia_t*, int* rank, int* world) { if (rank) *rank = 0; if (world) *world = 0; return 0; }

@@ -684,12 +684,62 @@ def _pivchol_setup(orc, name):
     return pc, c, coords, y, perm, co, nn, ct, cp, a, cases.pivchol_rank(pc)
 
 
-def _preconditioner_context(orc, pc, c, coords, co, ct, var, a, rank):
-    """orc.pivoted_cholesky_preconditioner, or -- pc = "fitc" -- orc.fitc_preconditioner with the inducing points the reference's generator draws (orc.vif_setup)."""
+def _preconditioner_context(orc, pc, c, coords, co, ct, var, a, rank, t=50, seed_rand=1):
+    """orc.pivoted_cholesky_preconditioner, or -- pc = "fitc" -- orc.fitc_preconditioner with the inducing points the reference's generator draws (orc.vif_setup);
+    t: the columns of rand_vec_trace_I2_ = the largest number of probes an evaluation inside the context may use."""
     if pc.get("pc") == "fitc":
         ip = orc.vif_setup(coords, c["m"], rank, c["ordering"], c["seed"])[3]
-        return orc.fitc_preconditioner(co, ip, ct, var, a)
-    return orc.pivoted_cholesky_preconditioner(co, ct, var, a, rank=rank)
+        return orc.fitc_preconditioner(co, ip, ct, var, a, num_rand_vec=t, seed_rand=seed_rand)
+    return orc.pivoted_cholesky_preconditioner(co, ct, var, a, rank=rank, num_rand_vec=t, seed_rand=seed_rand)
+
+
+@pytest.mark.parametrize("key", sorted(cases.LAPLACE_PIVCHOL_PROBE_CASES))
+def test_oracle_low_rank_preconditioners_match_the_reference_above_50_probes(orc, key):
+    """num_rand_vec_trace > 50 (a user setting of GPB_SetOptimConfig): the oracle inside a context with as many columns of rand_vec_trace_I2_ as probes against the
+    reference's own CalcGradPars at cases.LAPLACE_TIGHT (tests/golden/laplace_pivchol_probes_ref.npz, oracle/make_golden.py laplace_pivchol_probes): value 1e-9,
+    gradient 1e-8, the tolerances of the 50-probe fixtures above."""
+    name, t = cases.LAPLACE_PIVCHOL_PROBE_CASES[key]
+    g = np.load(os.path.join(GOLD, "laplace_pivchol_probes_ref.npz"))
+    pc, c, coords, y, perm, co, nn, ct, cp, a, rank = _pivchol_setup(orc, name)
+    tight = dict(cg_delta_conv=cases.LAPLACE_TIGHT["cg_delta_conv"], delta_conv_mode=cases.LAPLACE_TIGHT["delta_conv_mode_finding"])
+    with _preconditioner_context(orc, pc, c, coords, co, ct, cp[0], a, rank, t):
+        nll_t, grad_t = orc.vecchia_laplace_grad(co, nn, ct, cp[0], a, y[perm], likelihood=pc["lik"], num_rand_vec=t, **tight)
+    ref, ref_v = g[key + "_grad_direct"], float(g[key + "_negll_direct"])
+    print("oracle vs reference %s: value %.3e gradient %.3e (relative)" % (key, abs(nll_t - ref_v) / abs(ref_v), np.abs(grad_t - ref).max() / np.abs(ref).max()))
+    assert grad_t.shape == ref.shape
+    np.testing.assert_allclose(grad_t, ref, rtol=1e-8, atol=1e-8 * np.abs(ref).max())
+    assert abs(nll_t - ref_v) <= 1e-9 * abs(ref_v), (nll_t, ref_v)
+
+
+@pytest.mark.parametrize("name", ["pc_logit_n2000", "fitc_logit_n1500_r100"])
+def test_oracle_refuses_more_probes_than_its_preconditioner_context_has(orc, name):
+    """The k x t normals rand_vec_trace_I2_ belong to the context: 52 probes inside a context built for 50 used to read 2 k doubles past that buffer and return other
+    numbers (9.5e-6 / 2e-3 off in value / gradient on pc_logit_n2000 at rank 23).  Now: ValueError; with a 52-column context the evaluation returns."""
+    pc, c, coords, y, perm, co, nn, ct, cp, a, rank = _pivchol_setup(orc, name)
+    with _preconditioner_context(orc, pc, c, coords, co, ct, cp[0], a, rank):
+        with pytest.raises(ValueError, match="more probe vectors"):
+            orc.vecchia_laplace_grad(co, nn, ct, cp[0], a, y[perm], likelihood=pc["lik"], num_rand_vec=52)
+        with pytest.raises(ValueError, match="more probe vectors"):
+            orc.vecchia_laplace_logit(co, nn, ct, cp[0], a, y[perm], likelihood=pc["lik"], num_rand_vec=52)
+        v50, _ = orc.vecchia_laplace_logit(co, nn, ct, cp[0], a, y[perm], likelihood=pc["lik"], num_rand_vec=48)      # fewer probes than columns: fine
+        assert np.isfinite(v50)
+    with _preconditioner_context(orc, pc, c, coords, co, ct, cp[0], a, rank, 52):
+        v, g2 = orc.vecchia_laplace_grad(co, nn, ct, cp[0], a, y[perm], likelihood=pc["lik"], num_rand_vec=52)
+    assert np.isfinite(v) and np.all(np.isfinite(g2))
+
+
+def test_oracle_vifdu_context_refuses_more_probes_than_it_has(orc):
+    """orc.vif_laplace with "vifdu": rand_vec_trace_P_ (k x t) and rand_vec_trace_I3_ (n x t) belong to the context in the same way."""
+    rng = np.random.default_rng(2)
+    coords = rng.uniform(size=(300, 2))
+    y = (rng.uniform(size=300) < 0.5).astype(np.float64)
+    perm, co, nn, ip, ip2 = orc.vif_setup(coords, 10, 20, "none", 1, num_ind_points_preconditioner=20)
+    with orc.vif_laplace(co, nn, ip, 0, 1.0, 5.0, "vifdu", num_rand_vec=10) as ctx:
+        f = ctx.factor
+        with pytest.raises(ValueError, match="more probe vectors"):
+            orc.vecchia_laplace_logit(co, nn, 0, 1.0, 5.0, y[perm], factor=(f["A"], f["D"]), num_rand_vec=12)
+        v, info = orc.vecchia_laplace_logit(co, nn, 0, 1.0, 5.0, y[perm], factor=(f["A"], f["D"]), num_rand_vec=10)
+    assert info["rc"] == 0 and np.isfinite(v)
 
 
 @pytest.mark.parametrize("name", sorted(cases.LAPLACE_PIVCHOL_CASES))

@@ -51,10 +51,11 @@ def _state(orc, pc):
     return st, c, coords, y, perm, co, nn, ct, rank
 
 
-def _orc_context(orc, pc, c, coords, co, ct, var, a, rank):
+def _orc_context(orc, pc, c, coords, co, ct, var, a, rank, t=50, seed_rand=1):
+    """The oracle's preconditioner context with t columns of rand_vec_trace_I2_: the evaluations inside it may use up to t probes (more raises)."""
     if pc.get("pc") == "fitc":
-        return orc.fitc_preconditioner(co, orc.vif_setup(coords, c["m"], rank, c["ordering"], c["seed"])[3], ct, var, a)
-    return orc.pivoted_cholesky_preconditioner(co, ct, var, a, rank=rank)
+        return orc.fitc_preconditioner(co, orc.vif_setup(coords, c["m"], rank, c["ordering"], c["seed"])[3], ct, var, a, num_rand_vec=t, seed_rand=seed_rand)
+    return orc.pivoted_cholesky_preconditioner(co, ct, var, a, rank=rank, num_rand_vec=t, seed_rand=seed_rand)
 
 
 @pytest.mark.parametrize("name", sorted(cases.LAPLACE_PIVCHOL_CASES))
@@ -235,22 +236,77 @@ def test_pivoted_cholesky_that_meets_its_error_bound_before_its_rank(gpb, orc):
     st.close()
 
 
-@pytest.mark.parametrize("name,t,rank", [("pc_logit_n2000", 4, 37), ("pc_logit_n2000", 20, 50), ("pc_logit_n2000", 36, 23), ("pc_logit_n2000", 48, 50),
-                                         ("fitc_logit_n1500_r100", 20, 100), ("fitc_logit_n1500_r100", 48, 100)])
-def test_block_kernels_of_the_low_rank_part_at_other_probe_counts_and_ranks(gpb, orc, name, t, rank):
-    """The block forms of L'(W X) and X - L x2 run on v_mfma_f64_16x16x4_f64 (pivchol_kernels.hip: pc_ltwx_mfma_kernel / pc_combine_mfma_kernel<CT>) with CT = 1, 2 or 4 tiles of
-    16 block-vector columns per launch row -- chosen by the number of probe chunks -- and 16-column tiles of L.  The fixtures run t = 50 probes (13 chunks: CT = 4, one launch row,
-    last tile a quarter full); here 1, 5, 9 and 12 chunks (CT = 1, 2, 4) and ranks that are no multiple of 16 or 4, value and gradient against the oracle with the same probes.
-    Open (scripts/gpu_probe_counts.py, profiles/r06_probe_counts_*): with MORE than 50 probes device and oracle part ways for the low-rank preconditioners
-    (5e-5 at 52 probes -- the same 13 chunks as the pinned 50 -- while "vadu" agrees to 6e-13 at every count), so neither side is pinned there."""
+# (chunks = ceil(t / 4) blocks of 4 probes.)  More than 8 chunks: one launch per group of 16 chunks, the pointers to X / part / x2 / out moved by the group.
+_PROBES_BY_LAUNCH_SHAPE = (52, 64, 68, 100, 132)      # 13 chunks | 16: one full group | 17: a second group of ONE chunk | 25 | 33: three groups
+_BLOCK_KERNEL_CASES = ([("pc_logit_n2000", 4, 37), ("pc_logit_n2000", 20, 50), ("pc_logit_n2000", 36, 23), ("pc_logit_n2000", 48, 50),
+                        ("fitc_logit_n1500_r100", 20, 100), ("fitc_logit_n1500_r100", 48, 100)]
+                       + [(name, t, rank) for name, rank in (("pc_logit_n2000", 50), ("pc_logit_n2000", 23), ("fitc_logit_n1500_r100", 100)) for t in _PROBES_BY_LAUNCH_SHAPE]
+                       # pc_ltwx_mfma_kernel takes 256 columns of L per pass: the last column of the first pass, the first pass full, ONE column in the second, a partial tile there
+                       + [("pc_logit_n2000", 50, rank) for rank in (255, 256, 257, 300)])
+
+
+def _device_against_oracle(orc, name, t, rank):
     pc = dict(cases.LAPLACE_PIVCHOL_CASES[name], rank=rank)
     st, c, coords, y, perm, co, nn, ct, rk = _state(orc, pc)
     assert rk == rank
     var, rho = c["cov_pars"][0][0], c["cov_pars"][0][1]
     a = RC[ct] / rho
     nll, grad = st.laplace_eval_grad(ct, var, a, num_rand_vec=t, **cases.LAPLACE_TIGHT)
-    with _orc_context(orc, pc, c, coords, co, ct, var, a, rank):
+    with _orc_context(orc, pc, c, coords, co, ct, var, a, rank, t):
         on, og = orc.vecchia_laplace_grad(co, nn, ct, var, a, y[perm], likelihood=pc["lik"], num_rand_vec=t, **TIGHT_ORC)
+    print("device vs oracle %s t=%d rank=%d: value %.3e gradient %.3e (relative)" % (name, t, rank, abs(nll - on) / abs(on), np.abs(grad - og).max() / np.abs(og).max()))
     assert abs(nll - on) <= 1e-8 * abs(on), (nll, on)
     np.testing.assert_allclose(grad, og, rtol=1e-8, atol=1e-8 * np.abs(og).max())
+    st.close()
+
+
+@pytest.mark.parametrize("name,t,rank", _BLOCK_KERNEL_CASES)
+def test_block_kernels_of_the_low_rank_part_at_other_probe_counts_and_ranks(gpb, orc, name, t, rank):
+    """The block forms of L'(W X) and X - L x2 run on v_mfma_f64_16x16x4_f64 (pivchol_kernels.hip: pc_ltwx_mfma_kernel / pc_combine_mfma_kernel<CT>) with CT = 1, 2 or 4 tiles of
+    16 block-vector columns per launch row -- chosen by the number of probe chunks -- and 16-column tiles of L.  The fixtures run t = 50 probes (13 chunks: CT = 4, one launch,
+    last tile a quarter full); here 1, 5, 9 and 12 chunks (CT = 1, 2, 4) and ranks that are no multiple of 16 or 4; more than 50 probes, where the launches split into groups of
+    16 chunks (_PROBES_BY_LAUNCH_SHAPE); and ranks around 256, where pc_ltwx_mfma_kernel makes a second pass over the columns of L.  Value and gradient against the oracle
+    with the same probes: the oracle's context is built with num_rand_vec = t (a context with fewer columns of rand_vec_trace_I2_ than probes raises; the oracle itself is
+    pinned to the reference above 50 probes by tests/test_oracle_golden.py on tests/golden/laplace_pivchol_probes_ref.npz)."""
+    _device_against_oracle(orc, name, t, rank)
+
+
+@pytest.mark.parametrize("key", sorted(cases.LAPLACE_PIVCHOL_PROBE_CASES))
+def test_value_and_gradient_match_the_reference_above_50_probes(gpb, orc, key):
+    """num_rand_vec_trace > 50 (a user setting of GPB_SetOptimConfig) against the reference's own CalcGradPars at cases.LAPLACE_TIGHT
+    (tests/golden/laplace_pivchol_probes_ref.npz, oracle/make_golden.py laplace_pivchol_probes): value and gradient 1e-8, as test_value_and_gradient_match_the_reference."""
+    name, t = cases.LAPLACE_PIVCHOL_PROBE_CASES[key]
+    pc = cases.LAPLACE_PIVCHOL_CASES[name]
+    g = np.load(os.path.join(GOLD, "laplace_pivchol_probes_ref.npz"))
+    st, c, coords, y, perm, co, nn, ct, rank = _state(orc, pc)
+    cp = c["cov_pars"][0]
+    nll, grad = st.laplace_eval_grad(ct, cp[0], RC[ct] / cp[1], num_rand_vec=t, **cases.LAPLACE_TIGHT)
+    ref, ref_v = g[key + "_grad_direct"], float(g[key + "_negll_direct"])
+    print("device vs reference %s: value %.3e gradient %.3e (relative)" % (key, abs(nll - ref_v) / abs(ref_v), np.abs(grad - ref).max() / np.abs(ref).max()))
+    assert grad.shape == ref.shape
+    np.testing.assert_allclose(grad, ref, rtol=1e-8, atol=1e-8 * np.abs(ref).max())
+    assert abs(nll - ref_v) <= 1e-8 * abs(ref_v), (nll, ref_v)
+    st.close()
+
+
+@pytest.mark.parametrize("rank", [420, 512])
+def test_ranks_whose_small_operands_pass_64_kb_of_lds(gpb, orc, rank):
+    """pc_small_kernel (x2 = M y, y = the slices' partial sums of L'(W X)) keeps y in LDS.  It used to keep the four quarter sums of the slices there as well, whatever the
+    rank: k * nc * 40 bytes of dynamic LDS with nc = 4 columns per chunk -- rank 420: 67 200 bytes, rank 512: 81 920 bytes, against the 65 536 bytes a launch may ask for
+    without raising the kernel's limit first (nothing did, and nothing checked: the form held for k <= 409 only, while the rank is bounded by n alone).  Where the 40
+    bytes per element do not fit, one thread now adds the four quarters of its element in registers: k * nc * 8 bytes (rank 420: 13 440, rank 512: 16 384), which holds
+    for k <= 2048; laplace_set_preconditioner refuses more (test_rank_beyond_the_limit_of_the_small_kernel_is_refused).  The same sums in the same order either way.
+    20 probes (5 chunks: CT = 2)."""
+    _device_against_oracle(orc, "pc_logit_n2000", 20, rank)
+
+
+def test_rank_beyond_the_limit_of_the_small_kernel_is_refused(gpb):
+    """k * 4 * 8 bytes of LDS for the small operand of a chunk: k <= 2048 within the 64 KB of a launch; laplace_set_preconditioner names the limit."""
+    from gpboost_amd import shim
+    rng = np.random.default_rng(0)
+    co = rng.uniform(size=(2100, 2))
+    st = shim.VecchiaState(co, 5)
+    st.laplace_set_preconditioner("pivoted_cholesky", 2048)
+    with pytest.raises(gpb.GPBoostError, match="at most 2048"):
+        st.laplace_set_preconditioner("pivoted_cholesky", 2049)
     st.close()

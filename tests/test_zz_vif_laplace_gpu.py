@@ -145,6 +145,39 @@ def test_gradient_matches_the_reference_and_the_oracle(gpb, orc, name):
     st.close()
 
 
+@pytest.mark.parametrize("t", [52, 68])
+def test_value_and_gradient_match_the_oracle_above_50_probes(gpb, orc, t):
+    """More than 50 probe vectors on the "fitc" path of a VIF x non-Gaussian model: 13 chunks of 4 probes (one launch of the block kernels of pivchol_kernels.hip) and 17
+    (a second launch for a group of ONE chunk, with moved pointers).  Value and gradient against orc.vif_laplace_grad with the same t probes, two mode findings as in
+    test_gradient_matches_the_reference_and_the_oracle: 1e-8, the tolerance of the values and gradients of this file."""
+    from gpboost_amd import shim
+    name = "vifl_u2d_n1500_exp_m15_k40_logit"
+    c = cases.VIF_LAPLACE_CASES[name]
+    coords, y = cases.vif_laplace_data(name)
+    perm, co, nn, ip, ip2 = orc.vif_setup(coords, c["m"], c["k"], c["ordering"], c["seed"], num_ind_points_preconditioner=c["rank"])
+    ct = orc.cov_type_id(c["cov_function"], c["shape"])
+    var, rho = c["cov_pars"][0]
+    a = RC[ct] / rho
+    st = shim.VecchiaState(co, c["m"])
+    st.set_neighbors(nn)
+    st.vif_set_inducing_points(ip)
+    st.laplace_set_likelihood(c["lik"])
+    st.laplace_set_labels(y[perm].astype(np.int32))
+    st.laplace_set_preconditioner("fitc", c["rank"])
+    st.laplace_set_inducing_points(ip2)
+    st.laplace_eval_grad(ct, var, a, num_rand_vec=t, **cases.VIF_LAPLACE_TIGHT)
+    nll, grad = st.laplace_eval_grad(ct, var, a, num_rand_vec=t, reset_mode=False, **cases.VIF_LAPLACE_TIGHT)
+    okw = dict(likelihood=c["lik"], num_rand_vec=t, want_parts=True, cg_delta_conv=cases.VIF_LAPLACE_TIGHT["cg_delta_conv"],
+               delta_conv_mode=cases.VIF_LAPLACE_TIGHT["delta_conv_mode_finding"])
+    o0 = orc.vif_laplace_grad(co, nn, ip, ip2, ct, var, a, y[perm], **okw)
+    on, og, _ = orc.vif_laplace_grad(co, nn, ip, ip2, ct, var, a, y[perm], mode_init=o0[2]["mode"], **okw)
+    print("VIF fitc device vs oracle t=%d: value %.3e gradient %.3e (relative)" % (t, abs(nll - on) / abs(on), np.abs(grad - og).max() / np.abs(og).max()))
+    assert abs(nll - on) <= 1e-8 * abs(on), (nll, on)
+    assert grad.shape == og.shape
+    np.testing.assert_allclose(grad, og, rtol=0, atol=1e-8 * np.abs(og).max())
+    st.close()
+
+
 @pytest.mark.parametrize("fit", sorted(cases.VIF_LAPLACE_FITS))
 def test_fits_follow_the_reference(gpb, fit):
     """GPB_OptimCovPar on the device against the reference's own fit (tests/golden/vif_laplace_ref.npz, <fit>_*): lbfgs with the stochastic gradient (logit; gamma with its shape
