@@ -416,7 +416,7 @@ struct gpb_hip_hist {
   double* d_grad = nullptr; double* d_hess = nullptr;
   bool has_hess = false, has_grad = false;
   int* d_idx = nullptr; int idx_cap = 0;
-  long long* d_part_grad = nullptr; long long* d_part_hess = nullptr; uint32_t* d_part_cnt = nullptr; int part_chunks = 0;
+  long long* d_part_grad = nullptr; long long* d_part_hess = nullptr; int* d_part_hess_hi = nullptr; uint32_t* d_part_cnt = nullptr; int part_chunks = 0;
   unsigned long long* d_absmax = nullptr;                  // bits of max |grad|, max |hess|: the scale of the fixed-point histogram sums
   double* d_hist = nullptr; unsigned long long* d_cnt = nullptr;
   GpbComm comm;                                            // optional: data-parallel histogram all-reduce (rows sharded per rank)
@@ -2498,7 +2498,7 @@ int gpb_hip_hist_free(gpb_hip_hist_t* h) {
   for (auto& q : h->pin) if (q.p) { (void)hipHostUnregister(const_cast<void*>(q.p)); q.p = nullptr; }
   if (h->stream) (void)hipStreamDestroy(h->stream);
   dev_free(h->d_bins_rm); dev_free(h->d_bins_cm); dev_free(h->d_bin_offsets); dev_free(h->d_grad); dev_free(h->d_hess); dev_free(h->d_idx);
-  dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_cnt); dev_free(h->d_hist); dev_free(h->d_cnt); dev_free(h->d_absmax);
+  dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_hess_hi); dev_free(h->d_part_cnt); dev_free(h->d_hist); dev_free(h->d_cnt); dev_free(h->d_absmax);
   dev_free(h->d_pool); dev_free(h->d_fix); dev_free(h->d_meta3); dev_free(h->d_part); dev_free(h->d_split); dev_free(h->d_split_i); dev_free(h->d_used);
   dev_free(h->d_tree_red); dev_free(h->d_rows); dev_free(h->d_rows2); dev_free(h->d_counts); dev_free(h->d_root_rows);
   if (h->h_counts) (void)hipHostFree(h->h_counts); dev_free(h->d_ptags); dev_free(h->d_split2); dev_free(h->d_split2_i); dev_free(h->d_used2);
@@ -2551,9 +2551,25 @@ int gpb_hip_hist_set_gradients(gpb_hip_hist_t* h, const double* grad, const doub
   // sharded rows: ONE scale for all ranks -- the max over the ranks of the IEEE bit patterns (monotone for non-negative doubles) -- or every
   // rank would round its gradients to a different q and the sums would depend on how the rows were dealt to ranks
   if (h->comm.active() && comm_allreduce(h->comm, h->d_absmax, 2, GPB_T_U64, GPB_OP_MAX, h->stream)) return -1;
+  // A non-finite value anywhere: every sum of that array is reported as NaN (hist_convert_entry), whatever the integers are.  The integers must still not
+  // disturb the COUNT that shares the packed word with the gradient sum (an Inf / NaN bit pattern reaches into its bits), so the device copy is cleared.
+  unsigned long long mx[2] = {0ull, 0ull};
+  HIP_OK(hipMemcpyAsync(mx, h->d_absmax, sizeof(mx), hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
+  const unsigned long long kInfBits = 0x7ff0000000000000ull;
+  if (mx[0] >= kInfBits) HIP_OK(hipMemsetAsync(h->d_grad, 0, sizeof(double) * (size_t)h->n, h->stream));
+  if (hess && mx[1] >= kInfBits) HIP_OK(hipMemsetAsync(h->d_hess, 0, sizeof(double) * (size_t)h->n, h->stream));
+  if (mx[0] >= kInfBits || mx[1] >= kInfBits) HIP_OK(hipStreamSynchronize(h->stream));
   h->has_hess = hess != nullptr; h->has_grad = true;
   API_END();
+}
+
+// A chunk's gradient sum is one 64-bit word of at most 2^41 per row (hist_kernels.hip, "budgets"): more chunks when the usual count would leave more
+// rows than this in one (from n = 2.7e8 on with 128 chunks; multiples of 8 for the XCD-aware workgroup order)
+constexpr long long kHistMaxRowsPerChunk = 1LL << 21;
+static int hist_chunks_within_budget(int nchunks, int rows) {
+  if ((long long)nchunks * kHistMaxRowsPerChunk >= rows) return nchunks;
+  return (int)((((long long)rows + kHistMaxRowsPerChunk - 1) / kHistMaxRowsPerChunk + 7) & ~7LL);
 }
 
 static int hist_build_impl(gpb_hip_hist_t* h, const int32_t* data_indices, int32_t num_data, double const_hess,
@@ -2663,27 +2679,29 @@ static int hist_build_impl(gpb_hip_hist_t* h, const int32_t* data_indices, int32
   // and lane on ONE workgroup per CU lose more to the atomic rate than the shared row prologue saves -- and removed in round 4.)
   const bool rows_kernel = !h->has_hess && groups >= 4 && (long long)num_data >= 2048LL * h->num_cu;
   if (rows_kernel) nchunks = std::max(1, h->num_cu);      // one workgroup per CU and quad of feature groups (launches of whole quads, then the partial one)
+  nchunks = hist_chunks_within_budget(nchunks, num_data);
   const int rows_per_chunk = (num_data + nchunks - 1) / std::max(nchunks, 1);
   if (nchunks < 16 && rows_per_chunk > 0) nchunks = (num_data + rows_per_chunk - 1) / rows_per_chunk;
   if (nchunks < 1) nchunks = 1;
   if (h->part_chunks < nchunks) {
-    dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_cnt);
+    dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_hess_hi); dev_free(h->d_part_cnt);
     const size_t cnt = (size_t)nchunks * h->fpad * GPB_HIST_MAX_BIN;
     HIP_OK(hipMalloc(&h->d_part_grad, sizeof(long long) * cnt));
     HIP_OK(hipMalloc(&h->d_part_hess, sizeof(long long) * cnt));
+    HIP_OK(hipMalloc(&h->d_part_hess_hi, sizeof(int) * cnt));
     HIP_OK(hipMalloc(&h->d_part_cnt, sizeof(uint32_t) * cnt));
     h->part_chunks = nchunks;
   }
   gpb::HistKernelArgs a;
   a.bins_rm = h->d_bins_rm; a.data_indices = dev_indices ? dev_indices : (data_indices ? h->d_idx : nullptr); a.grad = h->d_grad;
   a.hess = h->has_hess ? h->d_hess : nullptr;
-  a.part_grad = h->d_part_grad; a.part_hess = h->d_part_hess; a.part_cnt = h->d_part_cnt;
+  a.part_grad = h->d_part_grad; a.part_hess = h->d_part_hess; a.part_hess_hi = h->d_part_hess_hi; a.part_cnt = h->d_part_cnt;
   a.grad_max_bits = h->d_absmax; a.hess_max_bits = h->d_absmax + 1;
   a.fpad = h->fpad; a.num_data = num_data; a.rows_per_chunk = std::max(rows_per_chunk, 1); a.nchunks = nchunks; a.num_features = h->F;
   a.use_rows_kernel = rows_kernel ? 1 : 0;
   a.bins_cm = h->d_bins_cm; a.rstride = h->rstride;
   gpb::HistReduceArgs r;
-  r.part_grad = h->d_part_grad; r.part_hess = h->d_part_hess; r.part_cnt = h->d_part_cnt; r.bin_offsets = h->d_bin_offsets;
+  r.part_grad = h->d_part_grad; r.part_hess = h->d_part_hess; r.part_hess_hi = h->d_part_hess_hi; r.part_cnt = h->d_part_cnt; r.bin_offsets = h->d_bin_offsets;
   r.grad_max_bits = h->d_absmax; r.hess_max_bits = h->d_absmax + 1;
   r.hist_out = d_target ? d_target : h->d_hist; r.cnt_out = h->d_cnt; r.fpad = h->fpad; r.nchunks = nchunks; r.num_features = h->F;
   r.const_hess = const_hess; r.has_hess = h->has_hess ? 1 : 0;
@@ -2717,22 +2735,24 @@ static int hist_build_planned(gpb_hip_hist_t* h, const int* rows_base, int seg_b
   const int chunk_mult = h->has_hess ? 2 : 4;
   int nchunks = std::max(1, std::min((ub_rows + 1023) / 1024, std::max(1, chunk_mult * h->num_cu / groups)));
   if (nchunks >= 16) nchunks &= ~7;
+  nchunks = hist_chunks_within_budget(nchunks, ub_rows);
   if (h->part_chunks < nchunks) {
-    dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_cnt);
+    dev_free(h->d_part_grad); dev_free(h->d_part_hess); dev_free(h->d_part_hess_hi); dev_free(h->d_part_cnt);
     const size_t cnt = (size_t)nchunks * h->fpad * GPB_HIST_MAX_BIN;
     HIP_OK(hipMalloc(&h->d_part_grad, sizeof(long long) * cnt));
     HIP_OK(hipMalloc(&h->d_part_hess, sizeof(long long) * cnt));
+    HIP_OK(hipMalloc(&h->d_part_hess_hi, sizeof(int) * cnt));
     HIP_OK(hipMalloc(&h->d_part_cnt, sizeof(uint32_t) * cnt));
     h->part_chunks = nchunks;
   }
   gpb::HistKernelArgs a;
   a.bins_rm = h->d_bins_rm; a.data_indices = rows_base; a.grad = h->d_grad; a.hess = h->has_hess ? h->d_hess : nullptr;
-  a.part_grad = h->d_part_grad; a.part_hess = h->d_part_hess; a.part_cnt = h->d_part_cnt;
+  a.part_grad = h->d_part_grad; a.part_hess = h->d_part_hess; a.part_hess_hi = h->d_part_hess_hi; a.part_cnt = h->d_part_cnt;
   a.grad_max_bits = h->d_absmax; a.hess_max_bits = h->d_absmax + 1;
   a.fpad = h->fpad; a.num_data = 0; a.rows_per_chunk = 1; a.nchunks = nchunks; a.num_features = h->F;
   a.seg_counts = h->d_counts; a.seg_begin = seg_begin; a.seg_cnt = seg_cnt; a.seg_gcnt = seg_gcnt; a.seg_min_data_in_leaf = min_data_in_leaf;
   gpb::HistReduceArgs r;
-  r.part_grad = h->d_part_grad; r.part_hess = h->d_part_hess; r.part_cnt = h->d_part_cnt; r.bin_offsets = h->d_bin_offsets;
+  r.part_grad = h->d_part_grad; r.part_hess = h->d_part_hess; r.part_hess_hi = h->d_part_hess_hi; r.part_cnt = h->d_part_cnt; r.bin_offsets = h->d_bin_offsets;
   r.grad_max_bits = h->d_absmax; r.hess_max_bits = h->d_absmax + 1;
   r.hist_out = d_target; r.cnt_out = nullptr; r.fpad = h->fpad; r.nchunks = nchunks; r.num_features = h->F;
   r.const_hess = const_hess; r.has_hess = h->has_hess ? 1 : 0;

@@ -237,7 +237,7 @@ extern "C" int gpb_hip_hist_grow_tree(gpb_hip_hist_t* h, int32_t num_leaves, dou
                              views_local ? &chunks_for_search : nullptr, bx)) return -1;
       gpb::ChildrenSearchArgs ca;
       if (chunks_for_search > 0) {      // no reduce launch: the search workgroups sum the chunk partials of their own feature (hist_kernels.h)
-        ca.part_grad = h->d_part_grad; ca.part_hess = h->d_part_hess; ca.part_cnt = h->d_part_cnt;
+        ca.part_grad = h->d_part_grad; ca.part_hess = h->d_part_hess; ca.part_hess_hi = h->d_part_hess_hi; ca.part_cnt = h->d_part_cnt;
         ca.grad_max_bits = h->d_absmax; ca.hess_max_bits = h->d_absmax + 1;
         ca.fpad = h->fpad; ca.nchunks = chunks_for_search; ca.has_hess = h->has_hess ? 1 : 0; ca.const_hess = const_hess;
       }

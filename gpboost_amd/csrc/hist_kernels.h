@@ -18,7 +18,7 @@ struct HistKernelArgs {
   const double* grad;       // [n]
   const double* hess;       // [n] or nullptr (constant hessian)
   long long* part_grad;     // [nchunks][fpad / 16][256 bins][16 features]  fixed-point sums (integers, units of q)
-  long long* part_hess;     // same layout  (non-constant hessian)
+  long long* part_hess;     // same layout  (non-constant hessian): the LOW 64 bits of the chunk's 96-bit two's-complement hessian sums (high words: part_hess_hi below)
   uint32_t* part_cnt;       // same layout
   const unsigned long long* grad_max_bits;   // IEEE bits of max |grad| / max |hess| over the rows set by gpb_hip_hist_set_gradients:
   const unsigned long long* hess_max_bits;   // they fix the power-of-two scale q of the fixed-point sums (launch_hist_absmax)
@@ -30,6 +30,9 @@ struct HistKernelArgs {
   int use_rows_kernel = 0;  // hist_build_rows_kernel (constant hessian, >= 4 feature groups): set by the host with a chunking of one workgroup per CU
   const int* seg_counts = nullptr;
   int seg_begin = 0, seg_cnt = 0, seg_gcnt = 0, seg_min_data_in_leaf = 0;
+  // HIGH 32 bits of the hessian partials, same layout as part_hess: at up to 2^51 per row one 64-bit word would wrap from 4096 rows of one bin in a chunk on
+  // (last member: the constant-hessian kernels' argument offsets are the ones they were tuned and measured with)
+  int* part_hess_hi = nullptr;
 };
 
 // regularisation of the split search beyond lambda_l2 (feature_histogram.hpp:137-161) + the parent_output argument of FindBestThreshold
@@ -55,6 +58,7 @@ struct ChildrenSearchArgs {
   // themselves (integer totals, converted as hist_reduce_kernel does: the same bits) and workgroup (f, 0) writes the entries to `smaller` -- no
   // reduce launch between build and search (round 4)
   const long long* part_grad = nullptr; const long long* part_hess = nullptr; const uint32_t* part_cnt = nullptr;
+  const int* part_hess_hi = nullptr;
   const unsigned long long* grad_max_bits = nullptr; const unsigned long long* hess_max_bits = nullptr;
   int fpad = 0, nchunks = 0, has_hess = 0; double const_hess = 1.0;
   int own_f0 = 0, own_f1 = 2147483647;   // feature-block exchange of the data-parallel grower: the features whose bins this rank holds (default: all)
@@ -74,6 +78,7 @@ struct HistReduceArgs {
   double const_hess; int has_hess;
   long long* limbs_out = nullptr;  // sharded handles: [5][limb_stride] integer totals {grad hi, grad lo, count, hess hi, hess lo} (word-major) INSTEAD of hist_out / cnt_out
   int limb_stride = 0;             // = total bins
+  const int* part_hess_hi = nullptr;   // high words of the hessian partials (HistKernelArgs); last member: the constant-hessian reduction keeps its argument offsets
 };
 
 hipError_t launch_hist_build(const HistKernelArgs& a, hipStream_t st);

@@ -34,7 +34,15 @@ namespace gpb {
 //   word = count << 53 | (sum k  mod 2^53)      -- sum over at most 1792 rows between two flushes: |sum k| <= 1792 * 2^41 < 2^52
 // Every 7 row-iterations (1792 rows of the workgroup) each thread drains "its" 16 words into 64-bit sums and 32-bit counts kept in
 // registers; those are written per chunk and summed over chunks -- exactly -- by hist_reduce_kernel.
-// Hessians (non-constant case) go to a second word without a count: |k_h| <= 2^51.
+// Hessians (non-constant case) go to a second word without a count: |k_h| <= 2^51, 1792 * 2^51 < 2^62 between two flushes.
+// Budgets of the stages behind the LDS words (tests/test_zz_hist_fixed_point_gpu.py runs the LDS words, the hessian partials and the totals at their edge against an
+// exact integer model; the gradient partial's budget takes effect from n = 2.7e8 rows on only and is covered by reading, not by a test):
+//   gradients: a chunk's sum is kept in 64 bits, |.| <= 2^41 * rows-per-chunk: the host keeps a chunk below 2^21 rows (kHistMaxRowsPerChunk, gpb_hip.cpp);
+//   hessians:  2^51 per row would pass 2^63 from 4096 rows of one bin in one chunk on (a two-bin feature, a dominant most-frequent bin, near-constant
+//              hessians), so a chunk's sum is kept in 96 bits -- 64 low + 32 high, 2^51 * 2^31 rows < 2^95 -- whatever the chunking and the bins are;
+//   totals:    two limbs of 32 bits in 64-bit words (Limbs): |total| / 2^32 <= 2^31 rows * 2^51 / 2^32 = 2^50, exact, converted once.
+// A non-finite gradient (hessian) makes every gradient (hessian) sum NaN; gpb_hip_hist_set_gradients then clears the device copy of that array, so that
+// no Inf / NaN bit pattern reaches the count field of the packed word: the counts stay exact.
 constexpr int kSumBits = 53;                                   // low bits of the packed word: the two's-complement sum
 // drain of one LDS word between the two barriers of a flush: one returning atomic (a plain read + write of the word was measured equal within the
 // run-to-run noise, 0.187 - 0.197 against 0.190 - 0.191 ms for the root pass at n = 1e7: profiles/r04_f_hist_flush_ab.txt)
@@ -103,10 +111,12 @@ __global__ __launch_bounds__(THREADS) void hist_build_kernel(HistKernelArgs a) {
   double inv_qh = 1.0;
   if constexpr (HAS_HESS) inv_qh = fixed_point_inv_q<true>(a.hess_max_bits);
   // thread t drains the words t, t + 256, ... (consecutive lanes, consecutive words): word w = (bin w / 16, feature w % 16)
-  long long rk[kOwn], rh[HAS_HESS ? kOwn : 1];
+  long long rk[kOwn];
+  unsigned long long rh[HAS_HESS ? kOwn : 1];       // hessians: 96-bit two's-complement sums, low 64 bits ...
+  int rhx[HAS_HESS ? kOwn : 1];                     // ... and high 32 bits (see "budgets" above)
   unsigned rc[kOwn];
 #pragma unroll
-  for (int i = 0; i < kOwn; ++i) { rk[i] = 0; rc[i] = 0u; if constexpr (HAS_HESS) rh[i] = 0; }
+  for (int i = 0; i < kOwn; ++i) { rk[i] = 0; rc[i] = 0u; if constexpr (HAS_HESS) { rh[i] = 0ull; rhx[i] = 0; } }
   auto flush = [&]() {          // one exchange per word: the old value comes back, zero goes in
     __syncthreads();
 #pragma unroll
@@ -115,7 +125,12 @@ __global__ __launch_bounds__(THREADS) void hist_build_kernel(HistKernelArgs a) {
       const long long sum = (long long)(v << (64 - kSumBits)) >> (64 - kSumBits);
       rk[i] += sum;
       rc[i] += (unsigned)((v - (unsigned long long)sum) >> kSumBits);
-      if constexpr (HAS_HESS) rh[i] += (long long)hist_drain_word(&s_hacc[i * THREADS + tid]);
+      if constexpr (HAS_HESS) {
+        const unsigned long long vh = hist_drain_word(&s_hacc[i * THREADS + tid]);     // |sum of <= 1792 k_h| < 2^62, two's complement
+        const unsigned long long lo = rh[i] + vh;
+        rhx[i] += (int)((long long)vh >> 63) + (lo < vh ? 1 : 0);                      // sign extension of vh + the carry out of the low word
+        rh[i] = lo;
+      }
     }
     __syncthreads();
   };
@@ -208,7 +223,7 @@ __global__ __launch_bounds__(THREADS) void hist_build_kernel(HistKernelArgs a) {
   for (int i = 0; i < kOwn; ++i) {
     a.part_grad[pbase + i * THREADS + tid] = rk[i];
     a.part_cnt[pbase + i * THREADS + tid] = rc[i];
-    if constexpr (HAS_HESS) a.part_hess[pbase + i * THREADS + tid] = rh[i];
+    if constexpr (HAS_HESS) { a.part_hess[pbase + i * THREADS + tid] = (long long)rh[i]; a.part_hess_hi[pbase + i * THREADS + tid] = rhx[i]; }
   }
 }
 
@@ -335,10 +350,16 @@ __global__ __launch_bounds__(512) void hist_build_rows_kernel(HistKernelArgs a) 
 
 // Sum of the chunk partials -- integers, so the total is exact and independent of the chunking.  A workgroup owns 64 consecutive words
 // (4 bins x 16 features) of one feature group; its 16 slices of 64 lanes take the chunks ch = slice, slice + 16, ... (coalesced 512-byte
-// segments, 4 loads in flight per lane).  A 64-bit partial is at most 2^41 * rows-per-chunk; the total over all chunks may pass 2^63,
-// so it is carried in two limbs (sum of the high 32 bits, sum of the low 32 bits) and converted once: fl(hi * 2^32 + lo) is the
-// correctly rounded integer total, and the scale q is a power of two.
-struct Limbs { long long hi = 0; unsigned long long lo = 0; __device__ void add(long long p) { hi += p >> 32; lo += (unsigned long long)(unsigned)p; } };
+// segments, 4 loads in flight per lane).  A gradient partial is one 64-bit word, at most 2^41 * rows-per-chunk < 2^62 (the host's chunking keeps
+// rows-per-chunk below 2^21); a hessian partial is at most 2^51 * rows-per-chunk and comes as 96 bits (low 64 + high 32).  The total over all chunks
+// may pass 2^63 either way, so it is carried in two limbs (sum of the bits from 2^32 up, sum of the low 32 bits; |hi| <= 2^50 for 2^31 rows) and converted
+// once: fl(hi * 2^32 + lo) is the correctly rounded integer total, and the scale q is a power of two.
+struct Limbs {
+  long long hi = 0; unsigned long long lo = 0;
+  __device__ void add(long long p) { hi += p >> 32; lo += (unsigned long long)(unsigned)p; }
+  // 96-bit two's-complement partial x * 2^64 + lo64 (lo64 unsigned)
+  __device__ void add96(long long lo64, int x) { hi += (long long)((unsigned long long)lo64 >> 32) + ((long long)x << 32); lo += (unsigned long long)(unsigned)lo64; }
+};
 // one histogram entry from its integer totals: q = 1 / inv_q exactly (powers of two); fl(hi * 2^32 + lo) is the correctly rounded integer
 // total.  A non-finite gradient / hessian anywhere makes the sums NaN (the reference's sums would be non-finite in the bins of those rows;
 // no tree can be grown from either)
@@ -376,14 +397,15 @@ __global__ __launch_bounds__(1024) void hist_reduce_kernel(HistReduceArgs a) {
     c += c0; c += c1; c += c2; c += c3;
     if constexpr (HAS_HESS) {
       const long long h0 = a.part_hess[p], h1 = a.part_hess[p + 16 * stride], h2 = a.part_hess[p + 32 * stride], h3 = a.part_hess[p + 48 * stride];
-      h.add(h0); h.add(h1); h.add(h2); h.add(h3);
+      const int x0 = a.part_hess_hi[p], x1 = a.part_hess_hi[p + 16 * stride], x2 = a.part_hess_hi[p + 32 * stride], x3 = a.part_hess_hi[p + 48 * stride];
+      h.add96(h0, x0); h.add96(h1, x1); h.add96(h2, x2); h.add96(h3, x3);
     }
   }
   for (; ch < a.nchunks; ch += 16) {
     const size_t p = p0 + (size_t)ch * stride;
     g.add(a.part_grad[p]);
     c += a.part_cnt[p];
-    if constexpr (HAS_HESS) h.add(a.part_hess[p]);
+    if constexpr (HAS_HESS) h.add96(a.part_hess[p], a.part_hess_hi[p]);
   }
   s_ghi[sl][l] = g.hi; s_glo[sl][l] = g.lo; s_c[sl][l] = c;
   if constexpr (HAS_HESS) { s_hhi[sl][l] = h.hi; s_hlo[sl][l] = h.lo; }
@@ -1065,7 +1087,7 @@ __device__ __forceinline__ void children_search_body(const ChildrenSearchArgs& a
       size_t p = (size_t)(f / GPB_HIST_FG) * kWords + (size_t)b * GPB_HIST_FG + (f % GPB_HIST_FG);
       for (int ch = 0; ch < a.nchunks; ++ch, p += stride) {
         g.add(a.part_grad[p]); c += a.part_cnt[p];
-        if (a.has_hess) h.add(a.part_hess[p]);
+        if (a.has_hess) h.add96(a.part_hess[p], a.part_hess_hi[p]);
       }
       if (a.has_hess) hist_convert_entry<true>(g, h, c, a.grad_max_bits, a.hess_max_bits, a.const_hess, s_sm + 2 * b, nullptr);
       else hist_convert_entry<false>(g, h, c, a.grad_max_bits, a.hess_max_bits, a.const_hess, s_sm + 2 * b, nullptr);
