@@ -16,7 +16,8 @@
 //   syrk_mfma_db_kernel      C -= L L^T on lower 128x128 tiles with v_mfma_f64_16x16x4_f64 (one wavefront per 64x64
 //                            quadrant = 16 accumulator tiles kept across the K loop, K staged through LDS in chunks of
 //                            64); used "narrow" (K = 64, inside a 512-wide block column) and "wide" (K = 512)
-//   trsv_lower_kernel        forward (and optionally backward) substitution + y^T Psi^-1 y + log-det
+//   trsv_fwd_step_kernel / trsv_bwd_step_kernel   forward / backward substitution, one launch per 64-wide block step;
+//                            trsv_sums_kernel: y^T Psi^-1 y + log-det
 #include "dev_common.h"
 #include "dense_kernels.h"
 
@@ -113,13 +114,18 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 //     chunk travels global -> registers while the MFMAs of the current one run, then registers -> the other LDS buffer, one barrier
 //     per chunk.  (r03_pmc.json for syrk_mfma_kernel: MFMA busy 0.38 of the kernel's cycles, 41 % of the wave cycles waiting: the
 //     staging of the single-buffered form is exposed.)
-// 1 / sqrt(x): v_rsq_f64 and one Newton step (relative error 1.5 delta^2 ~ 1e-16 for the instruction's delta ~ 2^-26), the form the point
-// kernel uses -- sqrt() followed by a division is two long dependent software sequences (~500 cycles per pivot, 64 pivots per block:
-// 13 of the 27 us of potrf_diag_kernel)
+// 1 / sqrt(x): v_rsq_f64 and two Newton steps, the form the point kernel uses -- sqrt() followed by a division is two long dependent software
+// sequences (~500 cycles per pivot, 64 pivots per block: 13 of the 27 us of potrf_diag_kernel).  One step is not enough: its result carries 1.5 delta^2
+// of the instruction's relative error delta, and delta reaches about 2^-25.4 (measured through the factor's backward error: 8 u in the pivot's inverse
+// square root, 20 u in column 3 of a 64 x 64 block, tests/test_zz_dense_kernels_gpu.py), not the 2^-26 first assumed.  After the second step the error
+// is 1.5 u from the step's own roundings for any delta below 2^-20.
 __device__ __forceinline__ double inv_sqrt_newton(double x) {
   const double y0 = __builtin_amdgcn_rsq(x);
-  const double e = __builtin_fma(-0.5 * x * y0, y0, 0.5);
-  return __builtin_fma(y0, e, y0);
+  const double hx = -0.5 * x;
+  const double e0 = __builtin_fma(hx * y0, y0, 0.5);
+  const double y1 = __builtin_fma(y0, e0, y0);
+  const double e1 = __builtin_fma(hx * y1, y1, 0.5);
+  return __builtin_fma(y1, e1, y1);
 }
 // Second forms of the two panel kernels.  potrf: the pivot's inverse square root by inv_sqrt_newton (27.7 -> 21.3 us
 // per block under the kernel trace).  trsm: the reciprocals of L11's diagonal once per workgroup (one division per lane, in parallel)
@@ -356,83 +362,6 @@ __global__ __launch_bounds__(1024) void dense_yrow_sums_kernel(const double* __r
   sred[tid] = lgd; __syncthreads();
   for (int w = 512; w >= 1; w >>= 1) { if (tid < w) sred[tid] += sred[tid + w]; __syncthreads(); }
   if (tid == 0) { out[0] = -P[(size_t)np * ld + np]; out[1] = 2.0 * sred[0]; }
-}
-
-// ---- triangular solves + reductions, one workgroup ----------------------------------------------
-// z = L^-1 y; out[0] = z^T z (= y^T Psi^-1 y), out[1] = 2 sum log L_ii; if x_out: x = L^-T z (= Psi^-1 y)
-__global__ __launch_bounds__(1024) void trsv_lower_kernel(const double* __restrict__ P, int n, int np, int ld,
-                                                          const double* __restrict__ y, double* __restrict__ z,
-                                                          double* __restrict__ out, double* __restrict__ x_out) {
-  __shared__ double sz[TB];
-  __shared__ double sred[1024];
-  __shared__ double sD[TB][TB + 1];       // the diagonal block of the current step (its 64 sequential steps read LDS, not HBM)
-  const int tid = threadIdx.x;
-  for (int i = tid; i < np; i += 1024) z[i] = i < n ? y[i] : 0.0;
-  __syncthreads();
-  for (int b0 = 0; b0 < np; b0 += TB) {
-    for (int e = tid; e < TB * TB; e += 1024) sD[e >> 6][e & 63] = P[(size_t)(b0 + (e >> 6)) * ld + b0 + (e & 63)];
-    __syncthreads();
-    // diagonal block: 64 sequential steps by the first wavefront
-    if (tid < TB) {
-      double zi = z[b0 + tid];
-      for (int k = 0; k < TB; ++k) {
-        const double lkk = sD[k][k];
-        const double zk = __shfl(zi, k, 64) / lkk;
-        if (tid == k) zi = zk;
-        if (tid > k) zi = __builtin_fma(-sD[tid][k], zk, zi);
-      }
-      sz[tid] = zi; z[b0 + tid] = zi;
-    }
-    __syncthreads();
-    // rows below: z[i] -= L[i][b0:b0+64] . z_block   (4 threads per row, 16 columns each)
-    const int sub = tid & 3;
-    for (int i = b0 + TB + (tid >> 2); i < np; i += 256) {
-      const double* row = P + (size_t)i * ld + b0 + sub * 16;
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc = __builtin_fma(row[k], sz[sub * 16 + k], acc);
-      acc += __shfl_xor(acc, 1, 64);
-      acc += __shfl_xor(acc, 2, 64);
-      if (sub == 0) z[i] -= acc;
-    }
-    __syncthreads();
-  }
-  double q = 0.0, lgd = 0.0;
-  for (int i = tid; i < n; i += 1024) { q = __builtin_fma(z[i], z[i], q); lgd += log(P[(size_t)i * ld + i]); }
-  sred[tid] = q; __syncthreads();
-  for (int w = 512; w >= 1; w >>= 1) { if (tid < w) sred[tid] += sred[tid + w]; __syncthreads(); }
-  if (tid == 0) out[0] = sred[0];
-  __syncthreads();
-  sred[tid] = lgd; __syncthreads();
-  for (int w = 512; w >= 1; w >>= 1) { if (tid < w) sred[tid] += sred[tid + w]; __syncthreads(); }
-  if (tid == 0) out[1] = 2.0 * sred[0];
-  if (x_out == nullptr) return;
-  __syncthreads();
-  // backward: L^T x = z, blocks from the bottom; x overwrites z
-  for (int b0 = np - TB; b0 >= 0; b0 -= TB) {
-    for (int e = tid; e < TB * TB; e += 1024) sD[e >> 6][e & 63] = P[(size_t)(b0 + (e >> 6)) * ld + b0 + (e & 63)];
-    __syncthreads();
-    if (tid < TB) {
-      double xi = z[b0 + tid];
-      for (int k = TB - 1; k >= 0; --k) {
-        const double lkk = sD[k][k];
-        const double xk = __shfl(xi, k, 64) / lkk;
-        if (tid == k) xi = xk;
-        if (tid < k) xi = __builtin_fma(-sD[k][tid], xk, xi);
-      }
-      sz[tid] = xi; z[b0 + tid] = xi;
-    }
-    __syncthreads();
-    // rows above: z[i] -= sum_k L[b0+k][i] x[b0+k]  (column access of L: coalesced across i)
-    for (int i = tid; i < b0; i += 1024) {
-      double acc = 0.0;
-#pragma unroll 8
-      for (int k = 0; k < TB; ++k) acc = __builtin_fma(P[(size_t)(b0 + k) * ld + i], sz[k], acc);
-      z[i] -= acc;
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < n; i += 1024) x_out[i] = z[i];
 }
 
 // ---- exact-GP gradient: the trace and the quadratic forms of CalcGradPars (re_model_template.h:2016-2040) in one pass --------
@@ -798,7 +727,7 @@ hipError_t launch_dense_grad(int cov, bool d3, const double4* pts, int n, int np
 }
 
 // ---- the same solves over many workgroups: one launch per 64-wide block step -------------------------------------------------
-// trsv_lower_kernel walks the whole triangle with ONE workgroup (49 ms at n = 16 384 next to a 68 ms factorisation).  Here step b of the
+// (The first form walked the whole triangle with ONE workgroup: 49 ms at n = 16 384 next to a 68 ms factorisation; it had no caller left and was removed.)  Here step b of the
 // forward substitution is one launch: every workgroup solves the 64 x 64 diagonal block against the current right-hand side block
 // redundantly (64 sequential steps of one wavefront out of LDS, the same arithmetic everywhere) and then subtracts L[i, block b] z_b
 // from ITS 256 rows below; the solved block goes to a separate vector, so no workgroup ever reads what another one writes in the same
@@ -884,10 +813,7 @@ __global__ __launch_bounds__(1024) void trsv_sums_kernel(const double* __restric
 // z (np) = L^-1 y, out = {z'z, log-det}; x_out (np, optional) = L^-T z; work: np doubles of scratch
 hipError_t launch_dense_solve(const double* P, int n, int np, int ld, const double* y, double* z, double* out, double* x_out,
                               hipStream_t st, double* work) {
-  if (work == nullptr) {          // no scratch: the one-workgroup form
-    hipLaunchKernelGGL(trsv_lower_kernel, dim3(1), dim3(1024), 0, st, P, n, np, ld, y, z, out, x_out);
-    return hipGetLastError();
-  }
+  if (work == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(trsv_init_kernel, dim3((np + 255) / 256), dim3(256), 0, st, y, n, np, work);
   for (int b0 = 0; b0 < np; b0 += TB) {
     const int below = np - b0 - TB;

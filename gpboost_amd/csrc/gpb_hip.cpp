@@ -2098,6 +2098,46 @@ int gpb_hip_vecchia_newton_leaf_values(gpb_hip_vecchia_t* h, const int32_t* leaf
 // launches of a block column's panel chain queue behind it -- made the n = 16 384 factorisation SLOWER, 65.0 against 43.9 ms (masks of 32 / 64 CUs were not honoured: 43.9 ms).
 static hipError_t create_lookahead_stream(hipStream_t* out) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
 
+// Test entry (tests/test_zz_dense_kernels_gpu.py): what launch_dense_cholesky leaves behind.  The row-major ld x ld matrix goes to the device as it is
+// (both triangles), the first ncols columns are factorised -- with the second stream and the two events of the look-ahead when lookahead != 0, with null
+// pointers otherwise -- and the whole array comes back: L in the lower triangle of the first ncols columns, the Schur complement in the lower triangle of
+// the rest, the strict upper triangle as uploaded.  *info is the device's failure word; info != 0 is NOT an error of this call.
+int gpb_hip_dense_cholesky_check(int32_t ld, int32_t ncols, int32_t lookahead, const double* M_host, double* out_host, int32_t* info) {
+  API_BEGIN();
+  if (!M_host || !out_host || !info) return fail("gpb_hip_dense_cholesky_check: null argument");
+  if (ld < 64 || ld % 64 != 0 || ld > 24000 || ncols < 1 || ncols > ld) return fail("gpb_hip_dense_cholesky_check: ld = %d (a multiple of 64, <= 24000), ncols = %d (1..ld)", ld, ncols);
+  if (check_device()) return -1;
+  struct Bufs {
+    double* P = nullptr; int* info = nullptr; hipStream_t st = nullptr, st2 = nullptr; hipEvent_t ev_panels = nullptr, ev_rest = nullptr;
+    ~Bufs() {
+      dev_free(P); dev_free(info);
+      if (ev_panels) (void)hipEventDestroy(ev_panels);
+      if (ev_rest) (void)hipEventDestroy(ev_rest);
+      if (st2) (void)hipStreamDestroy(st2);
+      if (st) (void)hipStreamDestroy(st);
+    }
+  } b;
+  const size_t bytes = sizeof(double) * (size_t)ld * ld;
+  HIP_OK(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
+  if (lookahead) {
+    HIP_OK(create_lookahead_stream(&b.st2));
+    HIP_OK(hipEventCreateWithFlags(&b.ev_panels, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&b.ev_rest, hipEventDisableTiming));
+  }
+  HIP_OK(hipMalloc(&b.P, bytes));
+  HIP_OK(hipMalloc(&b.info, sizeof(int)));
+  HIP_OK(hipMemsetAsync(b.info, 0, sizeof(int), b.st));
+  HIP_OK(hipMemcpyAsync(b.P, M_host, bytes, hipMemcpyHostToDevice, b.st));
+  HIP_OK(gpb::launch_dense_cholesky(b.P, ld, b.info, b.st, b.st2, b.ev_panels, b.ev_rest, ncols));
+  int dev_info = 0;
+  HIP_OK(hipMemcpyAsync(&dev_info, b.info, sizeof(int), hipMemcpyDeviceToHost, b.st));
+  HIP_OK(hipMemcpyAsync(out_host, b.P, bytes, hipMemcpyDeviceToHost, b.st));
+  HIP_OK(hipStreamSynchronize(b.st));
+  if (b.st2) HIP_OK(hipStreamSynchronize(b.st2));
+  *info = dev_info;
+  API_END();
+}
+
 // ------------------------------------------------------------------------------------------
 int gpb_hip_exact_create(int32_t n, int32_t d, const double* coords_colmajor, gpb_hip_exact_t** out) {
   API_BEGIN();

@@ -387,6 +387,57 @@ class ExactState(object):
                                                   _p(ya), _p(ms)))
         return out, ya, ms
 
+    def grad_terms(self, cov_type, var, a):
+        """-> array {y' Psi^-1 y, log|Psi|, 0, g1_var, g2_var, g1_range, g2_range} (gpb_hip_exact_grad_terms)"""
+        out = np.empty(7)
+        _shim_call(_lib().gpb_hip_exact_grad_terms(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(out)))
+        return out
+
+    def psi_inv_diag(self, cov_type, var, a):
+        """-> diag(Psi^-1), n entries (gpb_hip_exact_psi_inv_diag)"""
+        out = np.empty(self.n)
+        _shim_call(_lib().gpb_hip_exact_psi_inv_diag(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(out)))
+        return out
+
+    def predict(self, coords_pred, want_q, cov_type, var, a):
+        """coords_pred (n_pred, d) -> (C Psi^-1 y, C Psi^-1 C' (n_pred, n_pred) or None) on the transformed scale (gpb_hip_exact_predict)"""
+        cp = np.asarray(coords_pred, dtype=np.float64)
+        if cp.ndim == 1:
+            cp = cp.reshape(-1, 1)
+        assert cp.shape[1] == self.d
+        npred = cp.shape[0]
+        cm = np.asfortranarray(cp)
+        mean = np.empty(npred)
+        q = np.empty((npred, npred)) if want_q else None
+        _shim_call(_lib().gpb_hip_exact_predict(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), C.c_int(npred), _p(cm), _p(mean), _p(q)))
+        return mean, q
+
+
+def dense_cholesky_check(M, ncols=None, lookahead=False):
+    """The blocked Cholesky on the (ld, ld) matrix M, ld a multiple of 64, first ncols columns (gpb_hip_dense_cholesky_check).
+    -> (out, info): L, the Schur complement and the untouched strict upper triangle; info != 0 if a pivot was not positive."""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    ld = M.shape[0]
+    assert M.shape == (ld, ld)
+    out = np.empty_like(M)
+    info = C.c_int32(-1)
+    _shim_call(_lib().gpb_hip_dense_cholesky_check(C.c_int(ld), C.c_int(ld if ncols is None else int(ncols)), C.c_int(1 if lookahead else 0), _p(M), _p(out),
+                                                   C.byref(info)))
+    return out, int(info.value)
+
+
+def dense_spd_solve(M, rhs=None, sub0=None):
+    """M (n, n) symmetric positive definite, lower triangle significant (gpb_hip_dense_spd_solve).  -> (x = M^-1 rhs or None, rows / columns [sub0, n) of M^-1 or None)"""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    n = M.shape[0]
+    assert M.shape == (n, n)
+    r = None if rhs is None else np.ascontiguousarray(rhs, dtype=np.float64)
+    assert r is None or r.shape == (n,)
+    x = None if r is None else np.empty(n)
+    inv = None if sub0 is None else np.empty((n - int(sub0), n - int(sub0)))
+    _shim_call(_lib().gpb_hip_dense_spd_solve(C.c_int(n), _p(M), _p(r), _p(x), C.c_int(0 if sub0 is None else int(sub0)), _p(inv)))
+    return x, inv
+
 
 class LocalGroup(object):
     """In-process group of `world` ranks (threads of this process; their handles may share one device): the second transport behind the

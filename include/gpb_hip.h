@@ -371,6 +371,11 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_predict_joint_factor(gpb_hip_vecchia_t* h, in
  * positive definite. */
 GPB_HIP_EXPORT int gpb_hip_dense_spd_solve(int32_t n, const double* M_host, const double* rhs_host, double* x_host, int32_t sub0,
                                            double* inv_sub_host);
+/* Test entry: the blocked Cholesky itself on a host matrix, everything it leaves behind copied back.  M_host / out_host row-major ld x ld, ld a multiple
+ * of 64, 0 < ncols <= ld: the first ncols columns are factorised (lower triangle significant); out holds L in the lower triangle of those columns, the
+ * Schur complement C22 - L21 L21' in the lower triangle of the rest and the strict upper triangle unchanged.  lookahead != 0: with the second stream and
+ * the events of the look-ahead (used when ld > 1024), 0: without.  *info != 0: a pivot was not positive (the call itself still returns 0). */
+GPB_HIP_EXPORT int gpb_hip_dense_cholesky_check(int32_t ld, int32_t ncols, int32_t lookahead, const double* M_host, double* out_host, int32_t* info);
 
 /* Vecchia prediction 'order_obs_first_cond_all' (CalcPredVecchiaObservedFirstOrder with CondObsOnly = false,
  * src/GPBoost/Vecchia_utils.cpp:1701-2093): the prediction points condition on their num_neighbors_pred nearest points among the observed AND
