@@ -17,6 +17,7 @@
 #include "../../include/gpboost_c_api_subset.h"
 #include "../../include/gpb_hip.h"
 #include "gpb_optim.h"
+#include "lik_table.h"
 
 #include <algorithm>
 #include <cmath>
@@ -184,12 +185,9 @@ bool is_proportion_likelihood(const std::string& lik) {
 }
 bool is_logit_link(const std::string& lik) { return lik == "bernoulli_logit" || lik == "binomial_logit" || lik == "quasi_bernoulli_logit"; }
 bool is_probit_link(const std::string& lik) { return lik == "bernoulli_probit" || lik == "binomial_probit" || lik == "quasi_bernoulli_probit"; }
-int laplace_link_id(const std::string& lik) {
-  return is_probit_link(lik) ? 1 : (lik == "poisson" ? 2 : (lik == "gamma" ? 3 : (lik == "negative_binomial" ? 4 : (lik == "beta" ? 5 : (lik == "t" ? 6 : (lik == "lognormal" ? 7 : (lik == "gaussian_latent" ? 8 : 0)))))));
-}
-bool supported_non_gaussian(const std::string& lik) {
-  return lik == "bernoulli_logit" || lik == "bernoulli_probit" || lik == "poisson" || lik == "gamma" || lik == "negative_binomial" || lik == "beta" || lik == "t" || lik == "lognormal" || lik == "gaussian_latent" || is_proportion_likelihood(lik);
-}
+// what a likelihood is (id, kind of response, auxiliary parameters, their names) comes from lik_table.h; -1: not a likelihood of the Laplace path ("gaussian" included)
+int laplace_link_id(const std::string& lik) { return gpb::lik_id_of_name(lik.c_str()); }
+bool supported_non_gaussian(const std::string& lik) { return laplace_link_id(lik) >= 0; }
 // Likelihood::ParseLikelihoodAlias (likelihoods.h:10254-10275)
 // "<likelihood>_fix_df" -> "<likelihood>", *fix_df = true (ParseLikelihoodAliasEstimateAdditionalPars, likelihoods.h:10466-10471: the suffix is stripped from any name)
 std::string strip_fix_df(const std::string& lik, bool* fix_df) {
@@ -204,7 +202,7 @@ std::string parse_likelihood_alias(const std::string& lik) {
   if (lik == "quasi_binary" || lik == "quasi_binary_logit") return "quasi_bernoulli_logit";
   return lik;
 }
-int num_aux_of(const std::string& lik) { return lik == "t" ? 2 : ((lik == "gamma" || lik == "negative_binomial" || lik == "beta" || lik == "lognormal" || lik == "gaussian_latent") ? 1 : 0); }      // t: scale, df (likelihoods.h:398-407)
+int num_aux_of(const std::string& lik) { const int id = laplace_link_id(lik); return id < 0 ? 0 : gpb::lik_num_aux(id); }      // t: scale, df (likelihoods.h:398-407)
 // the model's auxiliary parameters to the device (Likelihood::SetAuxPars); a no-op for likelihoods without any
 // cg_preconditioner_type of the iterative methods (SetPropertiesLikelihood, re_model_template.h:7516-7524)
 int laplace_push_preconditioner(REModelHip* mdl) {
@@ -337,19 +335,21 @@ int laplace_upload_fixed_effects(REModelHip* mdl, const double* fixed_effects) {
 // response (validated against the likelihood) and fixed effects of the Vecchia-Laplace path, Vecchia order
 int laplace_upload_data(REModelHip* mdl, const double* y_data, const double* fixed_effects) {
   if (!y_data) return set_error("y_data is NULL: the HIP hot path evaluates the likelihood at the response passed in");
+  const int lik_id = laplace_link_id(mdl->likelihood);
+  if (lik_id < 0) return set_error("likelihood '%s' has no Laplace path", mdl->likelihood.c_str());
+  const gpb::Resp kind = gpb::lik_resp(lik_id);
   mdl->labels.resize(mdl->n);
-  const bool poisson = mdl->likelihood == "poisson" || mdl->likelihood == "negative_binomial";     // integer-valued responses >= 0
-  if (mdl->likelihood == "gamma" || mdl->likelihood == "beta" || mdl->likelihood == "t" || mdl->likelihood == "lognormal" || mdl->likelihood == "gaussian_latent") {      // likelihoods.h:1365-1373 (gamma, lognormal): strictly positive, real-valued; beta: :1403-1409, strictly inside (0, 1); t: any real value
-    const bool is_beta = mdl->likelihood == "beta", is_t = mdl->likelihood == "t" || mdl->likelihood == "gaussian_latent";      // (is_t: any finite real value)
+  const bool poisson = kind == gpb::Resp::kCount;     // integer-valued responses >= 0
+  if (gpb::lik_real_only(lik_id)) {      // likelihoods.h:1365-1373 (gamma, lognormal): strictly positive, real-valued; beta: :1403-1409, strictly inside (0, 1); t: any real value
     mdl->resp_real.resize(mdl->n);
     for (int k = 0; k < mdl->n; ++k) {
       const double yk = y_data[mdl->perm[k]];
-      if (is_beta) { if (!(yk > 0. && yk < 1.)) return set_error(" Must have 0 < y < 1 for the response variable ('y') for likelihood = '%s', found %g ", mdl->likelihood.c_str(), yk); }
-      else if (is_t) { if (!std::isfinite(yk)) return set_error("NaN or Inf in the response variable ('y') for likelihood = '%s' ", mdl->likelihood.c_str()); }
+      if (kind == gpb::Resp::kUnitInterval) { if (!(yk > 0. && yk < 1.)) return set_error(" Must have 0 < y < 1 for the response variable ('y') for likelihood = '%s', found %g ", mdl->likelihood.c_str(), yk); }
+      else if (kind == gpb::Resp::kFiniteReal) { if (!std::isfinite(yk)) return set_error("NaN or Inf in the response variable ('y') for likelihood = '%s' ", mdl->likelihood.c_str()); }
       else if (!(yk > 0.)) return set_error(" Must have y > 0 for the response variable ('y') for likelihood = '%s', found %g ", mdl->likelihood.c_str(), yk);
       mdl->resp_real[k] = yk; mdl->labels[k] = 0;
     }
-    if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, laplace_link_id(mdl->likelihood))) return shim_error();
+    if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, lik_id)) return shim_error();
     if (mdl->n_re > 0) {
       std::vector<double> grouped(mdl->n);
       for (int g = 0; g < mdl->n; ++g) grouped[g] = mdl->resp_real[mdl->dorder[g]];
@@ -369,7 +369,7 @@ int laplace_upload_data(REModelHip* mdl, const double* y_data, const double* fix
       if (yk < 0. || yk > 1. || !(yk == yk)) return set_error(" Must have 0 <= y <= 1 for the response variable ('y') for likelihood = '%s', found %g. Note that the response variable should be the proportion of successes / trials ", mdl->likelihood.c_str(), yk);
       mdl->resp_real[k] = yk; mdl->labels[k] = 0;
     }
-    if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, laplace_link_id(mdl->likelihood))) return shim_error();
+    if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, lik_id)) return shim_error();
     if (gpb_hip_vecchia_laplace_set_binomial(mdl->vh, binom ? 1 : 0)) return shim_error();
     if (mdl->n_re > 0) {
       std::vector<double> grouped(mdl->n);
@@ -395,7 +395,7 @@ int laplace_upload_data(REModelHip* mdl, const double* y_data, const double* fix
       return set_error("The response variable ('y') needs to be 0 or 1 for likelihood = '%s' ", mdl->likelihood.c_str());
     mdl->labels[k] = std::fabs(yk) < 1e-10 ? 0 : 1;
   }
-  if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, laplace_link_id(mdl->likelihood))) return shim_error();
+  if (gpb_hip_vecchia_laplace_set_likelihood(mdl->vh, lik_id)) return shim_error();
   if (gpb_hip_vecchia_laplace_set_binomial(mdl->vh, 0)) return shim_error();
   if (mdl->n_re > 0) {
     std::vector<int> grouped(mdl->n);
@@ -1502,10 +1502,11 @@ int GPB_SetOptimConfig(REModelHandle handle, double* init_cov_pars, double lr, d
   if (init_aux_pars && mdl->num_aux > 0) {
     if (mdl->num_aux_estim() < mdl->num_aux && !mdl->aux_set && !near(init_aux_pars[1], mdl->aux_pars[1]))       // likelihoods.h:2763-2768
       fprintf(stderr, "[gpboost_amd] Warning: The 'df' parameter provided in 'init_aux_pars' (= %g) and 'likelihood_additional_param' (= %g) are not equal. Will use the value provided in 'likelihood_additional_param' \n", init_aux_pars[1], mdl->aux_pars[1]);
+    const gpb::LikInfo& lk = gpb::kLik[laplace_link_id(mdl->likelihood)];      // (num_aux > 0: a likelihood of the table)
     for (int j = 0; j < mdl->num_aux; ++j) {
       mdl->init_aux[j] = init_aux_pars[j];                                     // init_aux_pars_ keeps what the caller passed (re_model.cpp:327-344)
       if (j >= mdl->num_aux_estim()) continue;                                 // SetAuxPars copies the first num_aux_pars_estim_ values only (likelihoods.h:2780-2789)
-      if (!(init_aux_pars[j] > 0.)) return set_error("The %s parameter is not > 0 (found %g)", mdl->likelihood == "t" ? (j == 0 ? "scale" : "df") : (mdl->likelihood == "lognormal" ? "log_variance" : "shape"), init_aux_pars[j]);
+      if (!(init_aux_pars[j] > 0.)) return set_error("The %s parameter is not > 0 (found %g)", j == 0 ? lk.aux_label_init : lk.aux2_label, init_aux_pars[j]);
       mdl->aux_pars[j] = init_aux_pars[j];
     }
     mdl->init_aux_given = true; mdl->aux_set = true;
@@ -3041,7 +3042,7 @@ int GPB_GetAuxPars(REModelHandle handle, double* aux_pars, char* out_str, bool c
     }   // (C_API_BEGIN's try block)
     catch (const std::exception& e) { return set_error("%s", e.what()); } catch (...) { return set_error("unknown exception"); }
   }
-  if (out_str) std::strcpy(out_str, mdl->likelihood == "t" ? "scale_SEP_df" : (mdl->likelihood == "beta" ? "precision" : (mdl->likelihood == "lognormal" ? "log_variance" : (mdl->likelihood == "gaussian_latent" ? "error_variance" : "shape"))));      // lognormal: likelihoods.h:507       // GetNamesAuxPars joins with "_SEP_" (likelihoods.h:2809-2814)         // names_aux_pars_ of gamma / negative_binomial (likelihoods.h:300, :319), beta (:380)
+  if (out_str) std::strcpy(out_str, gpb::kLik[laplace_link_id(mdl->likelihood)].aux_names);      // lognormal: likelihoods.h:507       // GetNamesAuxPars joins with "_SEP_" (likelihoods.h:2809-2814)         // names_aux_pars_ of gamma / negative_binomial (likelihoods.h:300, :319), beta (:380)
   return 0;
 }
 

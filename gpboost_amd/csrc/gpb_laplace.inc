@@ -10,6 +10,7 @@
 // Everything O(n) runs on the device (laplace_kernels.hip); the host keeps the loop counters, reads ONE residual norm
 // (or t of them) per CG iteration, and diagonalises the t small Lanczos tridiagonals at the end.
 #include "laplace_kernels.h"
+#include "lik_table.h"
 #include "pivchol_kernels.h"
 
 #include <chrono>
@@ -40,7 +41,7 @@ struct LaplaceState {
   // order) = CSR of a random effect's data in the order labels / fe are handed over (grouped by random effect); d_dptr = the same CSR in the
   // workspace's storage order with the data regrouped accordingly.  Empty = one datum per random effect.
   int n_data = 0; std::vector<int> re_ptr; int* d_dptr = nullptr; bool map_dirty = false;
-  int link = 0;                   // 0 = Bernoulli-logit, 1 = Bernoulli-probit, 2 = Poisson, 3 = gamma, 4 = negative_binomial (gpb_hip_vecchia_laplace_set_likelihood)
+  int link = gpb::kBernoulliLogit;   // a gpb::Lik: row of lik_table.h (gpb_hip_vecchia_laplace_set_likelihood)
   double log_norm_const = 0.;     // log_normalizing_constant_: part of every LogLikelihood() value (likelihoods.h:11290)
   // likelihoods with an auxiliary parameter (round 5): aux = shape of gamma / negative_binomial (gpb_hip_vecchia_laplace_set_aux_pars); gamma's
   // real-valued response (host copy in the order of `labels`, device copy in storage order); sum_log_y = aux_log_normalizing_constant_ of gamma
@@ -54,7 +55,7 @@ struct LaplaceState {
   // constant sum lgamma(w + 1) - lgamma(k + 1) - lgamma(w - k + 1), k = w y, of the binomial likelihoods (likelihoods.h:10612-10622, :10884-10886)
   bool real_resp = false, binomial = false;
   double aux2 = 2.0;              // second auxiliary parameter (t: the degrees of freedom; aux = its scale)
-  gpb::LikResp resp() const { return gpb::LikResp{ d_y, (link == 3 || link == 5 || link == 6 || link == 7 || link == 8 || real_resp) ? d_yd : nullptr, aux, weights.empty() ? nullptr : d_w, aux2 }; }
+  gpb::LikResp resp() const { return gpb::LikResp{ d_y, (gpb::lik_real_only(link) || real_resp) ? d_yd : nullptr, aux, weights.empty() ? nullptr : d_w, aux2 }; }
   double* d_vec = nullptr;        // 16 n-vectors (mode finding)
   double* d_rv = nullptr;         // probes N(0,1), layout [chunk of 4 columns][storage slot][4]
   double* d_blk = nullptr;        // 5 blocks of the same layout (R, Z, H, V, T)
@@ -453,12 +454,11 @@ int gpb_hip_vecchia_laplace_set_labels(gpb_hip_vecchia_t* h, const int32_t* y01)
   if (!h->lap) h->lap = new LaplaceState();
   LaplaceState* s = h->lap;
   const int nd = s->re_ptr.empty() ? h->n : s->n_data;
-  if (s->link == 3 || s->link == 5 || s->link == 6 || s->link == 7 || s->link == 8) return fail("%s: the response is real-valued (call gpb_hip_vecchia_laplace_set_response_real)", s->link == 3 ? "gamma" : (s->link == 5 ? "beta" : (s->link == 6 ? "t" : (s->link == 7 ? "lognormal" : "gaussian_latent"))));
+  const char* name = gpb::lik_name(s->link);
+  if (gpb::lik_real_only(s->link)) return fail("%s: the response is real-valued (call gpb_hip_vecchia_laplace_set_response_real)", name);
   for (int i = 0; i < nd; ++i) {
-    if (s->link == 2) {                 // Poisson: counts (likelihoods.h:1338-1350)
-      if (y01[i] < 0) return fail("poisson: the response must be >= 0 (found %d at Vecchia position %d)", y01[i], i);
-    } else if (s->link == 4) {          // negative_binomial: counts (:1338-1350)
-      if (y01[i] < 0) return fail("negative_binomial: the response must be >= 0 (found %d at Vecchia position %d)", y01[i], i);
+    if (gpb::lik_resp(s->link) == gpb::Resp::kCount) {      // likelihoods.h:1338-1350
+      if (y01[i] < 0) return fail("%s: the response must be >= 0 (found %d at Vecchia position %d)", name, y01[i], i);
     } else if (y01[i] != 0 && y01[i] != 1)
       return fail("bernoulli_logit / bernoulli_probit: labels must be 0 or 1 (found %d at Vecchia position %d)", y01[i], i);   // likelihoods.h:1321-1329
   }
@@ -471,20 +471,24 @@ int gpb_hip_vecchia_laplace_set_labels(gpb_hip_vecchia_t* h, const int32_t* y01)
   API_END();
 }
 
-// gamma: real-valued, strictly positive response (likelihoods.h:1365-1373), same order as gpb_hip_vecchia_laplace_set_labels takes its labels
+// real-valued response (its domain: Resp of lik_table.h), same order as gpb_hip_vecchia_laplace_set_labels takes its labels
 int gpb_hip_vecchia_laplace_set_response_real(gpb_hip_vecchia_t* h, const double* y) {
   API_BEGIN();
   if (!h || !y) return fail("null argument");
   if (!h->lap) h->lap = new LaplaceState();
   LaplaceState* s = h->lap;
-  if (s->link != 3 && s->link != 5 && s->link != 6 && s->link != 7 && s->link != 8 && s->link != 0 && s->link != 1)
+  if (!gpb::lik_accepts_real(s->link))
     return fail("gpb_hip_vecchia_laplace_set_response_real: a real-valued response is for gamma, beta, t, lognormal, gaussian_latent and for proportions under the logit / probit links (likelihood id %d)", s->link);
   const int nd = s->re_ptr.empty() ? h->n : s->n_data;
+  const char* name = gpb::lik_name(s->link);
   for (int i = 0; i < nd; ++i) {
-    if (s->link == 3 || s->link == 7) { if (!(y[i] > 0.)) return fail("%s: the response must be > 0 (found %g at Vecchia position %d)", s->link == 3 ? "gamma" : "lognormal", y[i], i); }      // likelihoods.h:1365-1373
-    else if (s->link == 5) { if (!(y[i] > 0. && y[i] < 1.)) return fail(" Must have 0 < y < 1 for the response variable ('y') for likelihood = 'beta', found %g ", y[i]); }      // likelihoods.h:1403-1409
-    else if (s->link == 6 || s->link == 8) { if (!std::isfinite(y[i])) return fail("%s: the response must be finite (found %g at Vecchia position %d)", s->link == 6 ? "t" : "gaussian_latent", y[i], i); }
-    else if (!(y[i] >= 0. && y[i] <= 1.)) return fail(" Must have 0 <= y <= 1 for the response variable ('y') (found %g at Vecchia position %d)", y[i], i);   // likelihoods.h:1330-1337
+    switch (gpb::lik_resp(s->link)) {      // likelihoods.h:1365-1373, :1403-1409, :1330-1337
+      case gpb::Resp::kPositiveReal: if (!(y[i] > 0.)) return fail("%s: the response must be > 0 (found %g at Vecchia position %d)", name, y[i], i); break;
+      case gpb::Resp::kUnitInterval: if (!(y[i] > 0. && y[i] < 1.)) return fail(" Must have 0 < y < 1 for the response variable ('y') for likelihood = '%s', found %g ", name, y[i]); break;
+      case gpb::Resp::kFiniteReal: if (!std::isfinite(y[i])) return fail("%s: the response must be finite (found %g at Vecchia position %d)", name, y[i], i); break;
+      case gpb::Resp::kBinaryOrProportion: if (!(y[i] >= 0. && y[i] <= 1.)) return fail(" Must have 0 <= y <= 1 for the response variable ('y') (found %g at Vecchia position %d)", y[i], i); break;
+      case gpb::Resp::kCount: break;      // refused above
+    }
   }
   s->real_resp = true;
   s->norm_dirty = true;
@@ -512,18 +516,19 @@ int gpb_hip_vecchia_laplace_set_weights(gpb_hip_vecchia_t* h, const double* w) {
   API_END();
 }
 
-// auxiliary parameters of the likelihood (gamma, negative_binomial: one, the shape; original scale, > 0): Likelihood::SetAuxPars (likelihoods.h:2622-2760)
+// auxiliary parameters of the likelihood (how many and which: lik_table.h; original scale, > 0): Likelihood::SetAuxPars (likelihoods.h:2622-2760)
 int gpb_hip_vecchia_laplace_set_aux_pars(gpb_hip_vecchia_t* h, const double* aux, int32_t num_aux) {
   API_BEGIN();
   if (!h || !aux) return fail("null argument");
   if (!h->lap) h->lap = new LaplaceState();
   LaplaceState* s = h->lap;
-  if (s->link < 3) return fail("gpb_hip_vecchia_laplace_set_aux_pars: likelihood id %d has no auxiliary parameters", s->link);
-  if (num_aux != (s->link == 6 ? 2 : 1)) return fail("gpb_hip_vecchia_laplace_set_aux_pars: %d parameters (gamma / negative_binomial have one, the shape; beta one, the precision; t two: scale, df; lognormal one, the variance of log y)", num_aux);
-  if (!(aux[0] > 0.) || !std::isfinite(aux[0])) return fail("The %s parameter is not > 0 (found %g)", s->link == 6 ? "scale" : (s->link == 7 ? "log_variance" : (s->link == 8 ? "error_variance" : "shape")), aux[0]);      // likelihoods.h:2649-2656
-  if (s->link == 6 && (!(aux[1] > 0.) || !std::isfinite(aux[1]))) return fail("The df parameter is not > 0 (found %g)", aux[1]);
+  const gpb::LikInfo& lk = gpb::kLik[s->link];
+  if (!lk.num_aux) return fail("gpb_hip_vecchia_laplace_set_aux_pars: likelihood id %d has no auxiliary parameters", s->link);
+  if (num_aux != lk.num_aux) return fail("gpb_hip_vecchia_laplace_set_aux_pars: %d parameters (gamma / negative_binomial have one, the shape; beta one, the precision; t two: scale, df; lognormal one, the variance of log y)", num_aux);
+  if (!(aux[0] > 0.) || !std::isfinite(aux[0])) return fail("The %s parameter is not > 0 (found %g)", lk.aux_label_set, aux[0]);      // likelihoods.h:2649-2656
+  if (lk.num_aux == 2 && (!(aux[1] > 0.) || !std::isfinite(aux[1]))) return fail("The %s parameter is not > 0 (found %g)", lk.aux2_label, aux[1]);
   if (aux[0] != s->aux) { s->aux = aux[0]; s->norm_dirty = true; s->grad_state = s->gvec_state = false; }
-  if (s->link == 6 && aux[1] != s->aux2) { s->aux2 = aux[1]; s->norm_dirty = true; s->grad_state = s->gvec_state = false; }
+  if (lk.num_aux == 2 && aux[1] != s->aux2) { s->aux2 = aux[1]; s->norm_dirty = true; s->grad_state = s->gvec_state = false; }
   API_END();
 }
 
@@ -561,7 +566,11 @@ int gpb_hip_vecchia_laplace_set_data_map(gpb_hip_vecchia_t* h, const int32_t* re
 int gpb_hip_vecchia_laplace_set_likelihood(gpb_hip_vecchia_t* h, int likelihood_id) {
   API_BEGIN();
   if (!h) return fail("null argument");
-  if (likelihood_id < 0 || likelihood_id > 8) return fail("gpb_hip_vecchia_laplace_set_likelihood: id %d (0 = bernoulli_logit, 1 = bernoulli_probit, 2 = poisson, 3 = gamma, 4 = negative_binomial, 5 = beta, 6 = t, 7 = lognormal, 8 = gaussian_latent)", likelihood_id);
+  if (!gpb::lik_valid(likelihood_id)) {
+    std::string ids;      // "0 = bernoulli_logit, 1 = bernoulli_probit, ..."
+    for (int i = 0; i < gpb::kNumLik; ++i) ids += (i ? ", " : "") + std::to_string(i) + " = " + gpb::lik_name(i);
+    return fail("gpb_hip_vecchia_laplace_set_likelihood: id %d (%s)", likelihood_id, ids.c_str());
+  }
   if (!h->lap) h->lap = new LaplaceState();
   if (h->lap->link != likelihood_id) { h->lap->has_y = false; h->lap->grad_state = h->lap->gvec_state = false; }   // labels are validated against the likelihood: set them again
   h->lap->link = likelihood_id;
@@ -1172,7 +1181,7 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
     to_storage(ys, s->labels);
     if (!s->d_y) HIP_OK(hipMalloc(&s->d_y, sizeof(int) * (size_t)nd));
     HIP_OK(hipMemcpy(s->d_y, ys.data(), sizeof(int) * (size_t)nd, hipMemcpyHostToDevice));
-    if (s->link == 3 || s->link == 5 || s->link == 6 || s->link == 7 || s->link == 8 || s->real_resp) {
+    if (gpb::lik_real_only(s->link) || s->real_resp) {
       if ((int)s->resp_real.size() != nd) return fail("the response was set for %d data, the data map has %d", (int)s->resp_real.size(), nd);
       std::vector<double> yr(nd);
       to_storage(yr, s->resp_real);
@@ -1198,40 +1207,31 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
     if (hw && (int)s->weights.size() != nd) return fail("the sample weights were set for %d data, the data map has %d", (int)s->weights.size(), nd);
     const double r = s->aux;
     s->log_norm_const = 0.;
-    if (s->link <= 1 && s->binomial) {
+    auto wt = [&](int i) { return hw ? s->weights[i] : 1.0; };
+    auto binomial_const = [&]() -> int {      // the binomial likelihoods under either link; plain / quasi Bernoulli: 0
+      if (!s->binomial) return 0;
       if (!hw || !s->real_resp) return fail("binomial likelihoods need the proportions (gpb_hip_vecchia_laplace_set_response_real) and the numbers of trials as sample weights");
-      double c = 0.;
-      for (int i = 0; i < nd; ++i) { const double w = s->weights[i], k = w * s->resp_real[i]; c += std::lgamma(w + 1.) - std::lgamma(k + 1.) - std::lgamma(w - k + 1.); }
-      s->log_norm_const = c;
-    } else if (s->link == 2) {
-      double c = 0.;
-      for (int i = 0; i < nd; ++i) c -= (hw ? s->weights[i] : 1.0) * std::lgamma((double)s->labels[i] + 1.0);     // log(y!): O(1) per observation whatever the count
-      s->log_norm_const = c;
-    } else if (s->link == 3) {
-      double sl = 0.;
-      for (int i = 0; i < nd; ++i) sl += (hw ? s->weights[i] : 1.0) * std::log(s->resp_real[i]);
-      s->sum_log_y = sl;
-      s->log_norm_const = (r == 1.0) ? 0.0 : (r - 1.0) * s->sum_log_y + nd * (r * std::log(r) - std::lgamma(r));
-    } else if (s->link == 7) {                                                         // lognormal, likelihoods.h:10623-10631, :10887-10889 (r = variance of log y)
-      double sl = 0.;
-      for (int i = 0; i < nd; ++i) sl += (hw ? s->weights[i] : 1.0) * std::log(s->resp_real[i]);
-      s->sum_log_y = sl;
-      s->log_norm_const = -sl - nd * (0.91893853320467274178 + 0.5 * std::log(r));
-    } else if (s->link == 8) {                                                         // gaussian_latent, likelihoods.h:10874-10876 (r = error variance)
-      s->log_norm_const = -nd * (0.91893853320467274178 + 0.5 * std::log(r));
-    } else if (s->link == 6) {                                                         // likelihoods.h:10869-10873 (r = scale, aux2 = df)
-      const double nu = s->aux2;
-      s->log_norm_const = nd * (-std::log(r) + std::lgamma((nu + 1.) / 2.) - 0.5 * std::log(nu) - std::lgamma(nu / 2.) - 0.5 * std::log(M_PI));
-    } else if (s->link == 5) {
-      s->log_norm_const = nd * std::lgamma(r);                                      // likelihoods.h:10866-10868
-    } else if (s->link == 4) {
-      double a1 = 0., slg = 0.;
-      for (int i = 0; i < nd; ++i) {
-        const double wi = hw ? s->weights[i] : 1.0;
-        a1 += wi * std::lgamma((double)s->labels[i] + r); slg += wi * std::lgamma((double)s->labels[i] + 1.0);
-      }
-      s->sum_lgamma_y1 = slg;
-      s->log_norm_const = a1 - s->sum_lgamma_y1 + nd * (r * std::log(r) - std::lgamma(r));
+      for (int i = 0; i < nd; ++i) { const double w = s->weights[i], k = w * s->resp_real[i]; s->log_norm_const += std::lgamma(w + 1.) - std::lgamma(k + 1.) - std::lgamma(w - k + 1.); }
+      return 0;
+    };
+    auto weighted_sum_log_y = [&]() { double sl = 0.; for (int i = 0; i < nd; ++i) sl += wt(i) * std::log(s->resp_real[i]); return sl; };
+    const double nu = s->aux2, gauss_const = nd * (0.91893853320467274178 + 0.5 * std::log(r));
+    switch (s->link) {
+      case gpb::kBernoulliLogit: if (binomial_const()) return -1; break;
+      case gpb::kBernoulliProbit: if (binomial_const()) return -1; break;
+      case gpb::kPoisson: for (int i = 0; i < nd; ++i) s->log_norm_const -= wt(i) * std::lgamma((double)s->labels[i] + 1.0); break;     // log(y!): O(1) per observation whatever the count
+      case gpb::kGamma: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = (r == 1.0) ? 0.0 : (r - 1.0) * s->sum_log_y + nd * (r * std::log(r) - std::lgamma(r)); break;
+      case gpb::kNegativeBinomial: {
+        double a1 = 0., slg = 0.;
+        for (int i = 0; i < nd; ++i) { a1 += wt(i) * std::lgamma((double)s->labels[i] + r); slg += wt(i) * std::lgamma((double)s->labels[i] + 1.0); }
+        s->sum_lgamma_y1 = slg;
+        s->log_norm_const = a1 - s->sum_lgamma_y1 + nd * (r * std::log(r) - std::lgamma(r));
+      } break;
+      case gpb::kBeta: s->log_norm_const = nd * std::lgamma(r); break;                                      // likelihoods.h:10866-10868
+      case gpb::kT: s->log_norm_const = nd * (-std::log(r) + std::lgamma((nu + 1.) / 2.) - 0.5 * std::log(nu) - std::lgamma(nu / 2.) - 0.5 * std::log(M_PI)); break;      // :10869-10873 (r = scale, aux2 = df)
+      case gpb::kLogNormal: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = -s->sum_log_y - gauss_const; break;      // :10623-10631, :10887-10889 (r = variance of log y)
+      case gpb::kGaussianLatent: s->log_norm_const = -gauss_const; break;                                   // :10874-10876 (r = error variance)
+      default: return fail("the normalising constant of likelihood id %d is missing", s->link);
     }
     s->norm_dirty = false;
   }
@@ -1406,7 +1406,8 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
 
   // ---- mode finding (likelihoods.h:3773-3978) ----
   // (gaussian_latent: the objective is quadratic in the mode -- ONE Newton step with ONE trial point, likelihoods.h:473-474)
-  const int maxit_mode_newton = s->link == 8 ? 1 : 1000, max_lr_shrink = s->link == 8 ? 1 : 20;        // :17316, :17322
+  const bool one_step = gpb::lik_single_newton_step(s->link);
+  const int maxit_mode_newton = one_step ? 1 : 1000, max_lr_shrink = one_step ? 1 : 20;        // :17316, :17322
   const double c_armijo = 1e-4, thr_zero_rhs = 1e-100;            // :17332; ZERO_RHS_CG_THRESHOLD
   if (reset_mode || !s->has_mode) HIP_OK(hipMemsetAsync(mode, 0, vb, st));
   if (!s->d_gvec) {
@@ -2716,7 +2717,7 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
   API_BEGIN();
   if (!h || !out4_host) return fail("null argument");
   LaplaceState* s = h->lap;
-  if (!s || s->link < 3) return fail("gpb_hip_vecchia_laplace_grad_aux_current: the likelihood has no auxiliary parameter");
+  if (!s || !gpb::lik_has_aux(s->link)) return fail("gpb_hip_vecchia_laplace_grad_aux_current: the likelihood has no auxiliary parameter");
   if (!s->grad_state || !s->gvec_state) return fail("the gradient wrt the auxiliary parameter needs the state of gpb_hip_vecchia_laplace_grad_current");
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n;
@@ -2727,20 +2728,25 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
   HIP_OK(hipMemcpyAsync(o3, s->d_o, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   const double r = s->aux;
-  if (s->link == 6 || s->link == 7 || s->link == 8) {
-    // gaussian_latent (link 8; one parameter, the error variance: CalcGradNegLogLikAuxPars :14262-14274 = 0.5 n - 0.5 / aux sum w resid^2, information 1 / aux,
+  if (!gpb::lik_info_depends_on_mode(s->link)) {
+    // gaussian_latent (one parameter, the error variance: CalcGradNegLogLikAuxPars :14262-14274 = 0.5 n - 0.5 / aux sum w resid^2, information 1 / aux,
     // d information / d log aux = -1 / aux :14881-14890): exactly the structure of lognormal.
-    // lognormal (link 7; one parameter, the variance of log y: CalcGradNegLogLikAuxPars :14275-14286, information 1 / aux, d information / d log aux = -1 / aux :14891-14900): the
+    // lognormal (one parameter, the variance of log y: CalcGradNegLogLikAuxPars :14275-14286, information 1 / aux, d information / d log aux = -1 / aux :14891-14900): the
     // structure of t below with ONE parameter.
     // t with the Fisher-Laplace approximation (likelihoods.h:6800-6815, grad_information_wrt_mode_non_zero_ = false): per parameter (log scale, log df)
     //   CalcGradNegLogLikAuxPars (:14241-14262) + 0.5 tr((Sigma^-1 + W)^-1 dW / d log aux), no implicit part; the trace by CalcLogDetStochDerivAuxParVecchia's vadu branch
     //   (:16838-16856) from U and PI_Z of the log-determinant's block CG, dW_r / d log aux = (sum of the weights of r's data) dFI / d log aux (:15369-15400).  out: 4 doubles per parameter.
-    const bool lognormal = s->link == 7 || s->link == 8;      // (one parameter, FI = 1 / aux)
-    const int n_aux_fl = lognormal ? 1 : 2;
+    const int n_aux_fl = gpb::lik_num_aux(s->link);
     const double nu = s->aux2, sigma2 = r * r;
-    const double g_scale = s->link == 8 ? -0.5 / r * o3[0] + 0.5 * nd : (lognormal ? o3[0] : o3[0] + nd);
+    // per parameter: CalcGradNegLogLikAuxPars from the kernel's sums; FI = the information per unit weight, dFI = d FI / d log(parameter)
+    double g_scale, FI = 1. / r, dFI[2] = { -1. / r, 0. };      // (lognormal, gaussian_latent: one parameter, FI = 1 / aux)
     const double g_df = (o3[1] + nd * (-1.0 + nu * (host_digamma((nu + 1.) / 2.) - host_digamma(nu / 2.)))) / -2.0;
-    const double dFI[2] = { lognormal ? -1. / r : -2. * (nu + 1.) / (nu + 3.) / sigma2, nu * 2. / sigma2 / (nu + 3.) / (nu + 3.) };
+    switch (s->link) {
+      case gpb::kT: g_scale = o3[0] + nd; FI = (nu + 1.) / (nu + 3.) / sigma2; dFI[0] = -2. * (nu + 1.) / (nu + 3.) / sigma2; dFI[1] = nu * 2. / sigma2 / (nu + 3.) / (nu + 3.); break;
+      case gpb::kLogNormal: g_scale = o3[0]; break;
+      case gpb::kGaussianLatent: g_scale = -0.5 / r * o3[0] + 0.5 * nd; break;
+      default: return fail("gpb_hip_vecchia_laplace_grad_aux_current: the Fisher-Laplace gradient of likelihood id %d is missing", s->link);
+    }
     const int NCB = 4, t = s->g_t, tch = (t + NCB - 1) / NCB, tc = tch * NCB;
     const size_t nb = (size_t)n * tc;
     hipStream_t st = h->stream;
@@ -2750,7 +2756,6 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
     const double *U = s->d_gblk, *PIZ = s->d_gblk + nb;
     const gpb::LapLevels lv = make_levels(h, s);
     // W_r = (sum of weights) FI  ->  the per-row weight sums are W / FI: dW / d log aux = W .* (dFI / FI)
-    const double FI = lognormal ? 1. / r : (nu + 1.) / (nu + 3.) / sigma2;
     if (s->pc_type != 0) {
       // pivoted_cholesky / fitc branches (:16800-16837) with dW = f W:  stochastic -f mean_c U_c' (W^-1 P^-1 Z_c) + n f;  control variate -f mean_c (W^-1 P^-1 Z_c)' W (W^-1 P^-1 Z_c)
       // against f [sum_i sdiag_i W_i - n] (pivoted_cholesky) / f [sum_i sdiag_i wp_i^2 / W_i - sum_i wp_i / W_i] (fitc); PIZ holds the probes Z here
@@ -2811,12 +2816,11 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
     return 0;
   }
   double nld;
-  if (s->link == 5) nld = -r * o3[0];      // beta: grad[0] = -precision * sum_d w_d (...) (likelihoods.h:14229-14241)
-  else if (s->link == 3) {        // CalcGradNegLogLikAuxPars, gamma (likelihoods.h:14189-14202)
-    nld = o3[0] - nd * (std::log(r) + 1.0 - host_digamma(r)) - s->sum_log_y;
-    nld *= r;
-  } else {                   // negative_binomial (:14203-14215)
-    nld = o3[0] + nd * r * (host_digamma(r) - std::log(r) - 1.0);
+  switch (s->link) {      // CalcGradNegLogLikAuxPars
+    case gpb::kBeta: nld = -r * o3[0]; break;      // grad[0] = -precision * sum_d w_d (...) (likelihoods.h:14229-14241)
+    case gpb::kGamma: nld = o3[0] - nd * (std::log(r) + 1.0 - host_digamma(r)) - s->sum_log_y; nld *= r; break;      // :14189-14202
+    case gpb::kNegativeBinomial: nld = o3[0] + nd * r * (host_digamma(r) - std::log(r) - 1.0); break;      // :14203-14215
+    default: return fail("gpb_hip_vecchia_laplace_grad_aux_current: the gradient of likelihood id %d is missing", s->link);
   }
   out4_host[0] = nld + 0.5 * o3[1] + o3[2];
   out4_host[1] = nld; out4_host[2] = 0.5 * o3[1]; out4_host[3] = o3[2];
@@ -2826,7 +2830,7 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
 int gpb_hip_vecchia_laplace_get_aux_pars(gpb_hip_vecchia_t* h, double* aux_out, int32_t* num_aux) {
   API_BEGIN();
   if (!h || !num_aux) return fail("null argument");
-  *num_aux = (h->lap && h->lap->link >= 3) ? (h->lap->link == 6 ? 2 : 1) : 0;
+  *num_aux = h->lap ? gpb::lik_num_aux(h->lap->link) : 0;
   if (aux_out && *num_aux) aux_out[0] = h->lap->aux;
   if (aux_out && *num_aux == 2) aux_out[1] = h->lap->aux2;
   API_END();

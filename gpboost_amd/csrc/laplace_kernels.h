@@ -50,8 +50,9 @@ struct CgScalars {         // per-column CG scalars on the device; part / part2:
 };
 int lap_cg_parts(int n);
 
-// the response as the likelihood kernels see it: int labels / counts (yi) or -- gamma -- real values (yd), and the likelihood's auxiliary parameter
-// (shape of gamma / negative_binomial; unused by the others)
+// the response as the likelihood kernels see it: int labels / counts (yi), or real values (yd: the likelihoods with a real-valued response, and
+// proportions under the logit / probit links; lik_table.h says which likelihood reads which), and the likelihood's auxiliary parameters
+// (aux, aux2: as many as the table's num_aux, in the order of its aux_names)
 struct LikResp { const int* yi; const double* yd; double aux; const double* w = nullptr; double aux2 = 2.0; };     // aux2: the second auxiliary parameter (t: degrees of freedom)     // w: sample weights per datum (storage order of the response), or nullptr
 hipError_t lap_newton_setup(int link, const double* mode, const LikResp& y, const double* fe, const double* D, int n, double* W, double* rhs, double* dw, double* rdw, hipStream_t st,
                             const int* dptr = nullptr);   // dptr (n + 1): repeated locations -- row i sums over the data y[dptr[i] .. dptr[i + 1]) (also below)
@@ -78,7 +79,8 @@ hipError_t lap_third_deriv(int link, const double* mode, const LikResp& y, const
 hipError_t lap_grad_F(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* sv, int n, double* out, hipStream_t st);
 hipError_t lap_grad_F_map(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* dW3, const double* sv, int n,
                           const int* dptr, double* out, hipStream_t st);      // repeated locations: per datum, storage order of the data
-// link 3 / 4: the three data sums of the gradient wrt log(aux) (laplace_kernels.hip: lik_aux_grad_kernel); dptr may be NULL (one datum per row)
+// likelihoods with auxiliary parameters (lik_has_aux; any other id: hipErrorInvalidValue): the three data sums of the gradient wrt log(aux)
+// (laplace_kernels.hip: lik_aux_grad_kernel); dptr may be NULL (one datum per row)
 hipError_t lap_aux_grad(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* dW3, const double* sv, int n,
                         const int* dptr, double* out3, hipStream_t st);
 hipError_t lap_range_deriv(const double4* pts, const int* nn, const double* A, int n, int m, int cov, int d3, double var, double a, double* dA, double* dD, hipStream_t st);

@@ -23,6 +23,7 @@
 #include <math.h>
 #include <algorithm>
 #include "laplace_kernels.h"
+#include "lik_table.h"
 
 namespace gpb {
 
@@ -42,7 +43,7 @@ __device__ __forceinline__ double sigmoid_stable(double x) {   // include/GPBoos
 __device__ __forceinline__ double softplus(double x) {         // DF_utils.h:57-60
   return log1p(exp(-fabs(x))) + fmax(x, 0.0);
 }
-// Bernoulli-probit (likelihood id 1): log Phi(x) exactly as GPBoost::normalLogCDF (DF_utils.h:74-92) and the inverse Mills ratio
+// Bernoulli-probit (kBernoulliProbit): log Phi(x) exactly as GPBoost::normalLogCDF (DF_utils.h:74-92) and the inverse Mills ratio
 // phi(z) / Phi(z) as InvMillsRatioNormalPhi (:94-98); with z = x for y = 1 and z = -x for y = 0:
 //   log p(y | x) = log Phi(z)                          (LogLikBernoulliProbit, likelihoods.h:11385-11392)
 //   d/dx         = +- phi(z) / Phi(z)                   (FirstDerivLogLikBernoulliProbit, :12459-12466)
@@ -62,22 +63,22 @@ __device__ __forceinline__ double normal_log_cdf(double x) {
 __device__ __forceinline__ double inv_mills_phi(double z) {
   return exp((-z * z / 2. - 0.91893853320467274178) - normal_log_cdf(z));
 }
-// per-observation pieces of the supported likelihoods: LINK 0 = Bernoulli-logit, 1 = Bernoulli-probit, 2 = Poisson (log link:
+// per-observation pieces of the supported likelihoods; LINK is a gpb::Lik, a row of lik_table.h: kBernoulliLogit, kBernoulliProbit, kPoisson (log link:
 // LogLikPoisson without the normalising constant, FirstDerivLogLikPoisson, SecondDerivNegLogLikPoisson; likelihoods.h:11407-11415,
-// :12481-12483, :13315-13317); round 5, likelihoods with an auxiliary parameter `aux` (shape): 3 = gamma (log link, real-valued response:
-// LogLikGamma :11872-11880, FirstDerivLogLikGamma :12485-12487, SecondDerivNegLogLikGamma :13319-13321), 4 = negative_binomial (LogLikNegBin
+// :12481-12483, :13315-13317); round 5, likelihoods with an auxiliary parameter `aux` (shape): kGamma (log link, real-valued response:
+// LogLikGamma :11872-11880, FirstDerivLogLikGamma :12485-12487, SecondDerivNegLogLikGamma :13319-13321), kNegativeBinomial (LogLikNegBin
 // :11882-11890, FirstDerivLogLikNegBin :12489-12492, SecondDerivNegLogLikNegBin :13323-13327).  The response reaches them as a double
-// (LikResp::at: the int label, or gamma's real value).
+// (resp_at: the int label or count, or the real value where the table's response kind says so).
 // (round 5: the logit / probit links also take a REAL response in [0, 1] -- binomial_logit / binomial_probit (y = successes / trials, the trials are the sample
 //  weights) and quasi_bernoulli_logit / _probit: LogLikBernoulliLogit<double> is linear in y; the probit terms are y f(1) + (1 - y) f(0) with the two Bernoulli
 //  branches, exactly the end points at y = 0 and y = 1: LogLikBinomialProbit :11394-11398, FirstDeriv :12468-12474, SecondDeriv :13293-13305, third :13800-13820)
 template <int LINK>
 __device__ __forceinline__ double resp_at(const LikResp& r, int d) {
-  if constexpr (LINK == 3 || LINK == 5 || LINK == 6 || LINK == 7 || LINK == 8) return r.yd[d];
-  else if constexpr (LINK == 0 || LINK == 1) return r.yd ? r.yd[d] : (double)r.yi[d];
+  if constexpr (lik_real_only(LINK)) return r.yd[d];
+  else if constexpr (lik_accepts_real(LINK)) return r.yd ? r.yd[d] : (double)r.yi[d];      // labels, or a proportion
   else return (double)r.yi[d];
 }
-// LINK 5 = beta (round 5, second slice; mean = sigmoid(location), precision = aux, real-valued response in (0, 1)): LogLikBeta likelihoods.h:11903-11913,
+// kBeta (round 5, second slice; mean = sigmoid(location), precision = aux, real-valued response in (0, 1)): LogLikBeta likelihoods.h:11903-11913,
 // FirstDerivLogLikBeta :12501-12507, SecondDerivNegLogLikBeta :13336-13346, third derivative :13892-13917.  digamma / trigamma / tetragamma as
 // src/GPBoost/DF_utils.cpp:82-201 (recurrence to >= 8.5 / 5 / 8, then the asymptotic series), sigmoid_stable_clamped as include/GPBoost/DF_utils.h:48-55.
 __device__ __forceinline__ double digamma_dev(double x);
@@ -101,11 +102,11 @@ __device__ __forceinline__ double sigmoid_clamped(double x) { double mu = sigmoi
 __device__ __forceinline__ double wt_at(const LikResp& r, int d) { return r.w ? r.w[d] : 1.0; }
 template <int LINK>
 __device__ __forceinline__ void lik_grad_info(double y, double x, double aux, double& grad, double& w, double aux2 = 0.0) {
-  if constexpr (LINK == 0) {
+  if constexpr (LINK == kBernoulliLogit) {
     const double p = sigmoid_stable(x);
     grad = y - p;                         // likelihoods.h:12477
     w = p * (1.0 - p);                    // :13307
-  } else if constexpr (LINK == 1) {
+  } else if constexpr (LINK == kBernoulliProbit) {
     if (y == 0.0 || y == 1.0) {
       const double z = y != 0.0 ? x : -x;
       const double r = inv_mills_phi(z);
@@ -116,17 +117,17 @@ __device__ __forceinline__ void lik_grad_info(double y, double x, double aux, do
       grad = y * r1 + (1.0 - y) * -r0;
       w = y * r1 * (x + r1) + (1.0 - y) * -r0 * (x - r0);
     }
-  } else if constexpr (LINK == 8) {       // gaussian_latent (round 6: the Gaussian likelihood through the Laplace machinery, aux = error variance): FirstDerivLogLikGaussian (likelihoods.h:12514-12516), information 1 / aux (:12956-12962)
+  } else if constexpr (LINK == kGaussianLatent) {       // gaussian_latent (round 6: the Gaussian likelihood through the Laplace machinery, aux = error variance): FirstDerivLogLikGaussian (likelihoods.h:12514-12516), information 1 / aux (:12956-12962)
     grad = (y - x) / aux;
     w = 1.0 / aux;
-  } else if constexpr (LINK == 7) {       // lognormal (round 5, fourth slice; mean of y = exp(location), aux = variance of log y): FirstDerivLogLikLogNormal (likelihoods.h:12534-12538), SecondDerivNegLogLikLogNormal (:13384-13386)
+  } else if constexpr (LINK == kLogNormal) {       // lognormal (round 5, fourth slice; mean of y = exp(location), aux = variance of log y): FirstDerivLogLikLogNormal (likelihoods.h:12534-12538), SecondDerivNegLogLikLogNormal (:13384-13386)
     grad = (log(y) - (x - 0.5 * aux)) / aux;
     w = 1.0 / aux;
-  } else if constexpr (LINK == 6) {       // t, fisher_laplace: FirstDerivLogLikT (likelihoods.h:12509-12512), FisherInformationT (:13358-13360): aux = scale, aux2 = df
+  } else if constexpr (LINK == kT) {       // t, fisher_laplace: FirstDerivLogLikT (likelihoods.h:12509-12512), FisherInformationT (:13358-13360): aux = scale, aux2 = df
     const double res = y - x;
     grad = (aux2 + 1.0) * res / (aux2 * aux * aux + res * res);
     w = (aux2 + 1.0) / (aux2 + 3.0) / (aux * aux);
-  } else if constexpr (LINK == 5) {
+  } else if constexpr (LINK == kBeta) {
     const double mu = sigmoid_clamped(x), logit_y = log(y) - log1p(-y);
     const double dig1 = digamma_dev((1.0 - mu) * aux), dig2 = digamma_dev(mu * aux);
     const double tri1 = trigamma_dev((1.0 - mu) * aux), tri2 = trigamma_dev(mu * aux);
@@ -134,15 +135,16 @@ __device__ __forceinline__ void lik_grad_info(double y, double x, double aux, do
     const double h1 = -aux * aux * mu * mu * (1.0 - mu) * (1.0 - mu) * (tri1 + tri2);
     const double h2 = aux * mu * (1.0 - mu) * (1.0 - 2.0 * mu) * (dig1 - dig2 + logit_y);
     w = -(h1 + h2);
-  } else if constexpr (LINK == 3) {
+  } else if constexpr (LINK == kGamma) {
     const double q = y * exp(-x);
     grad = aux * (q - 1.0);
     w = aux * q;
-  } else if constexpr (LINK == 4) {
+  } else if constexpr (LINK == kNegativeBinomial) {
     const double mu = exp(x), mr = mu + aux;
     grad = y - (y + aux) / mr * mu;
     w = (y + aux) * mu * aux / (mr * mr);
   } else {
+    static_assert(LINK == kPoisson, "lik_grad_info: a likelihood without its formulas");
     const double e = exp(x);
     grad = y - e;
     w = e;
@@ -150,21 +152,21 @@ __device__ __forceinline__ void lik_grad_info(double y, double x, double aux, do
 }
 template <int LINK>
 __device__ __forceinline__ double lik_loglik(double y, double x, double aux, double aux2 = 0.0) {
-  if constexpr (LINK == 0) return y * x - softplus(x);      // likelihoods.h:11401-11403
-  else if constexpr (LINK == 1) {
+  if constexpr (LINK == kBernoulliLogit) return y * x - softplus(x);      // likelihoods.h:11401-11403
+  else if constexpr (LINK == kBernoulliProbit) {
     if (y == 0.0 || y == 1.0) return normal_log_cdf(y != 0.0 ? x : -x);
     return y * normal_log_cdf(x) + (1.0 - y) * normal_log_cdf(-x);
   }
-  else if constexpr (LINK == 3) return -aux * (x + y * exp(-x));
-  else if constexpr (LINK == 4) return y * x - (y + aux) * log(exp(x) + aux);
-  else if constexpr (LINK == 7) { const double z = log(y) - (x - 0.5 * aux); return -0.5 * z * z / aux; }      // LogLikLogNormal (:11950-11958) without its constant
-  else if constexpr (LINK == 8) { const double res = y - x; return -res * res / 2.0 / aux; }                     // LogLikGaussian (:11927-11936) without its constant
-  else if constexpr (LINK == 6) return -(aux2 + 1.0) / 2.0 * log(1.0 + (y - x) * (y - x) / (aux2 * aux * aux));       // LogLikT (:11915-11925) without its constant
-  else if constexpr (LINK == 5) {
+  else if constexpr (LINK == kGamma) return -aux * (x + y * exp(-x));
+  else if constexpr (LINK == kNegativeBinomial) return y * x - (y + aux) * log(exp(x) + aux);
+  else if constexpr (LINK == kLogNormal) { const double z = log(y) - (x - 0.5 * aux); return -0.5 * z * z / aux; }      // LogLikLogNormal (:11950-11958) without its constant
+  else if constexpr (LINK == kGaussianLatent) { const double res = y - x; return -res * res / 2.0 / aux; }                     // LogLikGaussian (:11927-11936) without its constant
+  else if constexpr (LINK == kT) return -(aux2 + 1.0) / 2.0 * log(1.0 + (y - x) * (y - x) / (aux2 * aux * aux));       // LogLikT (:11915-11925) without its constant
+  else if constexpr (LINK == kBeta) {
     const double mu = sigmoid_clamped(x);
     return -lgamma(mu * aux) - lgamma((1.0 - mu) * aux) + (mu * aux - 1.0) * log(y) + ((1.0 - mu) * aux - 1.0) * log1p(-y);
   }
-  else return y * x - exp(x);
+  else { static_assert(LINK == kPoisson, "lik_loglik: a likelihood without its formula"); return y * x - exp(x); }
 }
 // digamma as GPBoost::digamma (src/GPBoost/DF_utils.cpp:82-125): small-argument approximation, recurrence up to x >= 8.5, de Moivre's expansion
 __device__ __forceinline__ double digamma_dev(double x) {
@@ -885,12 +887,12 @@ __global__ __launch_bounds__(1024) void lap_dot_kernel(const double* __restrict_
 // third derivative of the log-likelihood = d information / d location parameter (CalcFirstDerivInformationLocPar, likelihoods.h:13772-13800)
 template <int LINK>
 __device__ __forceinline__ double lik_third(double y, double x, double aux, double aux2 = 0.0) {
-  if constexpr (LINK == 0) { const double p = sigmoid_stable(x); return -p * (1.0 - p) * (2.0 * p - 1.0); }
-  else if constexpr (LINK == 2) return exp(x);
-  else if constexpr (LINK == 3) return -aux * y * exp(-x);                                            // likelihoods.h:13843-13849
-  else if constexpr (LINK == 4) { const double mu = exp(x), mr = mu + aux; return -(y + aux) * mu * aux * (mu - aux) / (mr * mr * mr); }   // :13870-13878
-  else if constexpr (LINK == 6 || LINK == 7 || LINK == 8) return 0.0;                                               // lognormal: constant information (:13929-13933); t, fisher_laplace: the information does not depend on the mode (:410-415)
-  else if constexpr (LINK == 5) {                                                                      // :13892-13917
+  if constexpr (LINK == kBernoulliLogit) { const double p = sigmoid_stable(x); return -p * (1.0 - p) * (2.0 * p - 1.0); }
+  else if constexpr (LINK == kPoisson) return exp(x);
+  else if constexpr (LINK == kGamma) return -aux * y * exp(-x);                                            // likelihoods.h:13843-13849
+  else if constexpr (LINK == kNegativeBinomial) { const double mu = exp(x), mr = mu + aux; return -(y + aux) * mu * aux * (mu - aux) / (mr * mr * mr); }   // :13870-13878
+  else if constexpr (!lik_info_depends_on_mode(LINK)) return 0.0;                                                   // lognormal: constant information (:13929-13933); t, fisher_laplace: the information does not depend on the mode (:410-415)
+  else if constexpr (LINK == kBeta) {                                                                      // :13892-13917
     const double mu = sigmoid_clamped(x), d = mu * (1.0 - mu), logit_y = log(y) - log1p(-y);
     const double dig1 = digamma_dev((1.0 - mu) * aux), dig2 = digamma_dev(mu * aux), tri1 = trigamma_dev((1.0 - mu) * aux), tri2 = trigamma_dev(mu * aux);
     const double tet1 = tetragamma_dev((1.0 - mu) * aux), tet2 = tetragamma_dev(mu * aux);
@@ -901,6 +903,7 @@ __device__ __forceinline__ double lik_third(double y, double x, double aux, doub
     return term_trigam + term_tetragam + -aux * gp * C;
   }
   else {
+    static_assert(LINK == kBernoulliProbit, "lik_third: a likelihood without its formula");
     const double x2 = x * x;
     if (y == 0.0) { const double q = inv_mills_phi(-x); return -q * (1.0 - x2 + q * (3.0 * x - 2.0 * q)); }
     const double r = inv_mills_phi(x);
@@ -974,17 +977,17 @@ __global__ __launch_bounds__(1024) void lik_aux_grad_kernel(const double* __rest
     const double mi = mode[i], svi = sv[i];
     for (int d = d0; d < d1; ++d) {
       const double x = fe ? mi + fe[d] : mi, yv = resp_at<LINK>(y, d), wd = wt_at(y, d);
-      if constexpr (LINK == 7) {       // lognormal: the data sum of CalcGradNegLogLikAuxPars (:14275-14286) -> e (dsum, isum unused)
+      if constexpr (LINK == kLogNormal) {       // lognormal: the data sum of CalcGradNegLogLikAuxPars (:14275-14286) -> e (dsum, isum unused)
         const double z = log(yv) - (x - 0.5 * r);
         e += wd * ((z + 1.0) * 0.5 - (z * z) / (2.0 * r));
-      } else if constexpr (LINK == 8) {       // gaussian_latent: sum w resid^2 of CalcGradNegLogLikAuxPars (:14262-14274) -> e; the host scales it by -0.5 / aux and adds 0.5 n
+      } else if constexpr (LINK == kGaussianLatent) {       // gaussian_latent: sum w resid^2 of CalcGradNegLogLikAuxPars (:14262-14274) -> e; the host scales it by -0.5 / aux and adds 0.5 n
         const double res = yv - x;
         e += wd * res * res;
-      } else if constexpr (LINK == 6) {       // t: the two data sums of CalcGradNegLogLikAuxPars (:14241-14262): e -> log scale, dsum -> log df (isum unused)
+      } else if constexpr (LINK == kT) {       // t: the two data sums of CalcGradNegLogLikAuxPars (:14241-14262): e -> log scale, dsum -> log df (isum unused)
         const double nu = y.aux2, nu_sigma2 = nu * r * r, res_sq = (yv - x) * (yv - x);
         e -= wd * (nu + 1.0) / (nu_sigma2 / res_sq + 1.0);
         dsum += wd * (-nu * log(1.0 + res_sq / nu_sigma2) + (nu + 1.0) / (1.0 + nu_sigma2 / res_sq));
-      } else if constexpr (LINK == 5) {       // CalcGradNegLogLikAuxPars beta (:14229-14241; the host multiplies by -precision), CalcSecondDerivLogLikFirstDerivInformationAuxPar beta (:14816-14845)
+      } else if constexpr (LINK == kBeta) {       // CalcGradNegLogLikAuxPars beta (:14229-14241; the host multiplies by -precision), CalcSecondDerivLogLikFirstDerivInformationAuxPar beta (:14816-14845)
         const double mu = sigmoid_clamped(x), dd = mu * (1.0 - mu), logit_y = log(yv) - log1p(-yv);
         const double dig1 = digamma_dev((1.0 - mu) * r), dig2 = digamma_dev(mu * r), tri1 = trigamma_dev((1.0 - mu) * r), tri2 = trigamma_dev(mu * r);
         const double tet1 = tetragamma_dev((1.0 - mu) * r), tet2 = tetragamma_dev(mu * r);
@@ -995,13 +998,14 @@ __global__ __launch_bounds__(1024) void lik_aux_grad_kernel(const double* __rest
         const double term3 = -r * dd * (1.0 - 2.0 * mu) * C, term4 = -r * r * dd * (1.0 - 2.0 * mu) * Dlt_tri;
         dsum = __builtin_fma(wd * (term1 + term2 + term3 + term4), diag, dsum);
         isum = __builtin_fma(wd * cross_deriv, svi, isum);
-      } else if constexpr (LINK == 3) {
+      } else if constexpr (LINK == kGamma) {
         const double q = yv * exp(-x);
         e += wd * (x + q);
         const double s2 = wd * (r * (q - 1.0));
         dsum = __builtin_fma(wd * (s2 + r), diag, dsum);       // (sic: the reference weights the first summand twice, likelihoods.h:14782-14783: w (w s2 + r))
         isum = __builtin_fma(s2, svi, isum);
       } else {
+        static_assert(LINK == kNegativeBinomial, "lik_aux_grad_kernel: a likelihood without its sums");
         const double mu = exp(x), mr = mu + r, yr = yv + r;
         e += wd * (r * (-digamma_dev(yr) + log(mr) + yr / mr));
         const double q = mu * r / (mr * mr);
@@ -1198,20 +1202,32 @@ __global__ __launch_bounds__(1024) void lap_sums3_kernel(const double* __restric
 
 // ---- launchers --------------------------------------------------------------------------------------------
 #define GRID1(n) dim3(((n) + 255) / 256), dim3(256)
+// The one run-time -> compile-time step of the likelihood id: calls f(IntC<L>{}) for L == link; false if link is no id in FIRST .. kNumLik - 1
+// (FIRST = kGamma serves lap_aux_grad: every id from there on has auxiliary parameters).  A new likelihood gets its case here.
+template <int FIRST, int L, class F>
+bool call_link(F& f) {
+  if constexpr (L >= FIRST) { f(IntC<L>{}); return true; }
+  else return false;
+}
+template <int FIRST = 0, class F>
+bool dispatch_link(int link, F&& f) {
+  static_assert(kNumLik == 9, "dispatch_link: one case per likelihood");
+  switch (link) {
+    case kBernoulliLogit: return call_link<FIRST, kBernoulliLogit>(f);
+    case kBernoulliProbit: return call_link<FIRST, kBernoulliProbit>(f);
+    case kPoisson: return call_link<FIRST, kPoisson>(f);
+    case kGamma: return call_link<FIRST, kGamma>(f);
+    case kNegativeBinomial: return call_link<FIRST, kNegativeBinomial>(f);
+    case kBeta: return call_link<FIRST, kBeta>(f);
+    case kT: return call_link<FIRST, kT>(f);
+    case kLogNormal: return call_link<FIRST, kLogNormal>(f);
+    case kGaussianLatent: return call_link<FIRST, kGaussianLatent>(f);
+    default: return false;
+  }
+}
 hipError_t lap_newton_setup(int link, const double* mode, const LikResp& y, const double* fe, const double* D, int n, double* W, double* rhs, double* dw, double* rdw, hipStream_t st,
                             const int* dptr) {
-  switch (link) {
-    case 0: hipLaunchKernelGGL(lik_newton_setup_kernel<0>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 1: hipLaunchKernelGGL(lik_newton_setup_kernel<1>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 2: hipLaunchKernelGGL(lik_newton_setup_kernel<2>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 3: hipLaunchKernelGGL(lik_newton_setup_kernel<3>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 4: hipLaunchKernelGGL(lik_newton_setup_kernel<4>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 5: hipLaunchKernelGGL(lik_newton_setup_kernel<5>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 6: hipLaunchKernelGGL(lik_newton_setup_kernel<6>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 7: hipLaunchKernelGGL(lik_newton_setup_kernel<7>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    case 8: hipLaunchKernelGGL(lik_newton_setup_kernel<8>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!dispatch_link(link, [&](auto L) { hipLaunchKernelGGL(lik_newton_setup_kernel<decltype(L)::value>, GRID1(n), 0, st, mode, y, fe, D, n, W, rhs, dw, rdw, dptr); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 // nc = columns per chunk of the block layout (1: plain column-major; 4: the probe block), ncol = number of chunks
@@ -1250,18 +1266,7 @@ hipError_t lap_scatter(const double* in, const int* sigma, int n, double* out, h
 }
 hipError_t lap_objective(int link, const double* x, const LikResp& y, const double* fe, const double* Bx, const double* D, int n, double* out2, hipStream_t st,
                          const int* dptr) {
-  switch (link) {
-    case 0: hipLaunchKernelGGL(lik_objective_kernel<0>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 1: hipLaunchKernelGGL(lik_objective_kernel<1>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 2: hipLaunchKernelGGL(lik_objective_kernel<2>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 3: hipLaunchKernelGGL(lik_objective_kernel<3>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 4: hipLaunchKernelGGL(lik_objective_kernel<4>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 5: hipLaunchKernelGGL(lik_objective_kernel<5>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 6: hipLaunchKernelGGL(lik_objective_kernel<6>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 7: hipLaunchKernelGGL(lik_objective_kernel<7>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    case 8: hipLaunchKernelGGL(lik_objective_kernel<8>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!dispatch_link(link, [&](auto L) { hipLaunchKernelGGL(lik_objective_kernel<decltype(L)::value>, dim3(1), dim3(1024), 0, st, x, y, fe, Bx, D, n, out2, dptr); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 // ---- the same solve WITHOUT level barriers: one launch for all levels [L0, L1) -------------------------------------------------------
@@ -1814,60 +1819,21 @@ hipError_t lap_dot(const double* x, const double* y, int n, double* out2, hipStr
 }
 
 hipError_t lap_third_deriv(int link, const double* mode, const LikResp& y, const double* fe, int n, double* dW3, hipStream_t st, const int* dptr) {
-  switch (link) {
-    case 0: hipLaunchKernelGGL(lik_third_kernel<0>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 1: hipLaunchKernelGGL(lik_third_kernel<1>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 2: hipLaunchKernelGGL(lik_third_kernel<2>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 3: hipLaunchKernelGGL(lik_third_kernel<3>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 4: hipLaunchKernelGGL(lik_third_kernel<4>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 5: hipLaunchKernelGGL(lik_third_kernel<5>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 6: hipLaunchKernelGGL(lik_third_kernel<6>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 7: hipLaunchKernelGGL(lik_third_kernel<7>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    case 8: hipLaunchKernelGGL(lik_third_kernel<8>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!dispatch_link(link, [&](auto L) { hipLaunchKernelGGL(lik_third_kernel<decltype(L)::value>, GRID1(n), 0, st, mode, y, fe, n, dW3, dptr); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 hipError_t lap_grad_F(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* sv, int n, double* out, hipStream_t st) {
-  switch (link) {
-    case 0: hipLaunchKernelGGL(lik_grad_F_kernel<0>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 1: hipLaunchKernelGGL(lik_grad_F_kernel<1>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 2: hipLaunchKernelGGL(lik_grad_F_kernel<2>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 3: hipLaunchKernelGGL(lik_grad_F_kernel<3>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 4: hipLaunchKernelGGL(lik_grad_F_kernel<4>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 5: hipLaunchKernelGGL(lik_grad_F_kernel<5>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 6: hipLaunchKernelGGL(lik_grad_F_kernel<6>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 7: hipLaunchKernelGGL(lik_grad_F_kernel<7>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    case 8: hipLaunchKernelGGL(lik_grad_F_kernel<8>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!dispatch_link(link, [&](auto L) { hipLaunchKernelGGL(lik_grad_F_kernel<decltype(L)::value>, GRID1(n), 0, st, mode, y, fe, dld, sv, n, out); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 hipError_t lap_grad_F_map(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* dW3, const double* sv, int n,
                           const int* dptr, double* out, hipStream_t st) {
-  switch (link) {
-    case 0: hipLaunchKernelGGL(lik_grad_F_map_kernel<0>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 1: hipLaunchKernelGGL(lik_grad_F_map_kernel<1>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 2: hipLaunchKernelGGL(lik_grad_F_map_kernel<2>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 3: hipLaunchKernelGGL(lik_grad_F_map_kernel<3>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 4: hipLaunchKernelGGL(lik_grad_F_map_kernel<4>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 5: hipLaunchKernelGGL(lik_grad_F_map_kernel<5>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 6: hipLaunchKernelGGL(lik_grad_F_map_kernel<6>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 7: hipLaunchKernelGGL(lik_grad_F_map_kernel<7>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    case 8: hipLaunchKernelGGL(lik_grad_F_map_kernel<8>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); break;
-    default: return hipErrorInvalidValue;
-  }
+  if (!dispatch_link(link, [&](auto L) { hipLaunchKernelGGL(lik_grad_F_map_kernel<decltype(L)::value>, GRID1(n), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 hipError_t lap_aux_grad(int link, const double* mode, const LikResp& y, const double* fe, const double* dld, const double* dW3, const double* sv, int n,
                         const int* dptr, double* out3, hipStream_t st) {
-  if (link == 3) hipLaunchKernelGGL(lik_aux_grad_kernel<3>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else if (link == 4) hipLaunchKernelGGL(lik_aux_grad_kernel<4>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else if (link == 5) hipLaunchKernelGGL(lik_aux_grad_kernel<5>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else if (link == 6) hipLaunchKernelGGL(lik_aux_grad_kernel<6>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else if (link == 7) hipLaunchKernelGGL(lik_aux_grad_kernel<7>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else if (link == 8) hipLaunchKernelGGL(lik_aux_grad_kernel<8>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3);
-  else return hipErrorInvalidValue;
+  if (!dispatch_link<kGamma>(link, [&](auto L) { hipLaunchKernelGGL(lik_aux_grad_kernel<decltype(L)::value>, dim3(1), dim3(1024), 0, st, mode, y, fe, dld, dW3, sv, n, dptr, out3); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
 hipError_t lap_factor_deriv(const double4* pts, const int* nn, const double* A, int n, int m, int cov, int d3, double var, double a, double diag_nn, double nug,

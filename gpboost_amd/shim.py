@@ -12,6 +12,12 @@ from .basic import GPBoostError, _lib, _shim_call
 
 MODE_NLL, MODE_FACTOR, MODE_GRAD = 0, 1, 2
 
+# likelihoods of the Vecchia-Laplace path, name -> (id of gpb_hip_vecchia_laplace_set_likelihood, number of auxiliary parameters): the rows of
+# csrc/lik_table.h (a test holds the two together).  The proportion likelihoods are the Bernoulli kernels with a real-valued response.
+_LIKELIHOODS = {"bernoulli_logit": (0, 0), "bernoulli_probit": (1, 0), "poisson": (2, 0), "gamma": (3, 1), "negative_binomial": (4, 1), "beta": (5, 1),
+                "t": (6, 2), "lognormal": (7, 1), "gaussian_latent": (8, 1)}
+_LIKELIHOODS.update({prefix + link: _LIKELIHOODS["bernoulli_" + link] for prefix in ("binomial_", "quasi_bernoulli_") for link in ("logit", "probit")})
+
 
 def _p(a, t=C.c_double):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
@@ -203,10 +209,8 @@ class VecchiaState(object):
         return out
 
     def laplace_set_likelihood(self, likelihood):
-        lid = {"bernoulli_logit": 0, "bernoulli_probit": 1, "poisson": 2, "gamma": 3, "negative_binomial": 4, "beta": 5, "t": 6, "lognormal": 7, "gaussian_latent": 8,
-               "binomial_logit": 0, "binomial_probit": 1, "quasi_bernoulli_logit": 0, "quasi_bernoulli_probit": 1}[likelihood]
+        lid, self._lap_num_aux = _LIKELIHOODS[likelihood]
         _shim_call(_lib().gpb_hip_vecchia_laplace_set_likelihood(self.h, C.c_int(lid)))
-        self._lap_link = lid
 
     def laplace_set_preconditioner(self, cg_preconditioner_type="vadu", rank=-999):
         """cg_preconditioner_type of the iterative methods: "vadu", "pivoted_cholesky" with `rank` columns, "fitc" with `rank` inducing points, or "vecchia_response"
@@ -252,7 +256,7 @@ class VecchiaState(object):
         """-> {gradient wrt log(shape), CalcGradNegLogLikAuxPars part, log-determinant part, implicit part} at the state of the last laplace_eval_grad."""
         o = np.zeros(8)          # 4 per auxiliary parameter (t has two: scale, df)
         _shim_call(_lib().gpb_hip_vecchia_laplace_grad_aux_current(self.h, _p(o)))
-        return o if getattr(self, "_lap_link", 0) == 6 else o[:4]
+        return o if getattr(self, "_lap_num_aux", 0) == 2 else o[:4]
 
     def laplace_set_fixed_effects(self, fixed_effects):
         """Offset of the location parameter, Vecchia order (None removes it)."""
@@ -288,10 +292,10 @@ class VecchiaState(object):
         parts = np.empty(8) if want_parts else None
         vecs = np.empty(2 * self.n) if want_parts else None
         _shim_call(_lib().gpb_hip_vecchia_laplace_grad_current(self.h, C.c_int(cg_max_num_it), C.c_double(cg_delta_conv), _p(g), _p(parts), _p(vecs)))
-        if getattr(self, "_lap_link", 0) == 6:      # t: d / d (log scale, log df)
+        if getattr(self, "_lap_num_aux", 0) == 2:      # t: d / d (log scale, log df)
             ga = self.laplace_grad_aux()
             g = np.array([g[0], g[1], ga[0], ga[4]])
-        elif getattr(self, "_lap_link", 0) >= 3:      # likelihoods with an auxiliary parameter: third entry = d / d log(aux)
+        elif getattr(self, "_lap_num_aux", 0) == 1:      # likelihoods with one auxiliary parameter: third entry = d / d log(aux)
             g = np.array([g[0], g[1], self.laplace_grad_aux()[0]])
         if want_parts:
             return -o[0], g, dict(per_par=parts.reshape(2, 4), dlogdet_dmode=vecs[:self.n], implicit_solve=vecs[self.n:])

@@ -422,7 +422,9 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_newton_leaf_values(gpb_hip_vecchia_t* h, cons
  *                             #CG-Lanczos iterations, log p(y|mode) - 0.5 mode^T Sigma^-1 mode,
  *                             ms factor, ms mode finding, ms log-determinant (host wall clock) };
  *               mode_host (optional) receives the mode, Vecchia order. */
-/* Likelihood of the Laplace path (set it BEFORE the labels, which are validated against it): 2 = "poisson" (counts >= 0; LogLikPoisson,
+/* Likelihood of the Laplace path (set it BEFORE the labels, which are validated against it).  The ids, and per id the kind of response, the number and
+ * names of the auxiliary parameters, are the rows of gpboost_amd/csrc/lik_table.h (enum gpb::Lik, table gpb::kLik): that table is the list, the notes
+ * below say where each likelihood's formulas come from.  2 = "poisson" (counts >= 0; LogLikPoisson,
  * FirstDerivLogLikPoisson, SecondDerivNegLogLikPoisson, likelihoods.h:11407-11415, :12481-12483, :13315-13317, and the normalising
  * constant -sum log(y!), :10750-10757), 0 = "bernoulli_logit" (default), 1 = "bernoulli_probit" (LogLikBernoulliProbit /
  * FirstDerivLogLikBernoulliProbit / SecondDerivNegLogLikBernoulliProbit, likelihoods.h:11385-11392, :12459-12466, :13282-13291,
