@@ -348,6 +348,7 @@ struct gpb_hip_vecchia {
   // spatially sorted gather (round 5): rank of every point in Morton order, the neighbour table rewritten into the sorted copy d_pts[n ..], built at the third
   // launch on a neighbour table (a prediction's temporary handle launches once), refreshed when the response in the records changed
   int* d_rank = nullptr; int* d_nn2 = nullptr; bool sorted_ready = false, gpts_dirty = false; int launches_on_table = 0;
+  int worker_cap = 0;             // gpb_hip_vecchia_set_worker_cap (test seam): at most this many persistent workers per point-kernel launch, 0 = no cap
   int sorted_mode = -1;           // gpb_hip_vecchia_set_sorted_gather: -1 as described, 0 never, 1 from the first launch on whatever n
   // a MODE_FACTOR launch into other buffers with observation-specific diagonal additions (the "vecchia_response" preconditioner's factor of W^-1 + Sigma,
   // gpb_laplace.inc pc_refresh): when set, vecchia_launch writes A / D / u there and takes the per-point diagonal entries var + nug[.] from it
@@ -748,6 +749,15 @@ int gpb_hip_vecchia_set_sorted_gather(gpb_hip_vecchia_t* h, int mode) {
   API_END();
 }
 
+/* Test seam: at most `cap` persistent worker workgroups per point-kernel launch (0 = no cap, the default grid). */
+int gpb_hip_vecchia_set_worker_cap(gpb_hip_vecchia_t* h, int32_t cap) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (cap < 0) return fail("gpb_hip_vecchia_set_worker_cap: cap = %d (0 = no cap)", cap);
+  h->worker_cap = cap;
+  API_END();
+}
+
 int gpb_hip_vecchia_get_neighbors(gpb_hip_vecchia_t* h, int32_t* nn) {
   API_BEGIN();
   if (!h || !nn) return fail("null argument");
@@ -916,6 +926,7 @@ static int vecchia_launch(gpb_hip_vecchia_t* h, int mode, int cov_type, double v
   } else {
     // ONE launch per evaluation: persistent worker workgroups + a finisher workgroup that adds up their sums (vecchia_kernels.hip)
     k.ngroups = (h->i_end - h->i_begin + 15) / 16;
+    k.max_workers = h->worker_cap;
     k.out = h->d_out; k.out_user = out_dev; k.out_host = host_slot_dev ? host_slot_dev : h->h_out;
     HIP_OK(gpb::launch_vecchia_point_kernel(mode, cov_type, h->d == 3, k, h->stream));
     if (ev1) HIP_OK(hipEventRecord(ev1, h->stream));

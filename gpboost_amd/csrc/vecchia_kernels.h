@@ -56,6 +56,7 @@ struct VecchiaKernelArgs {
   double* out = nullptr;               // [GPB_NUM_PARTIALS] the launch's sums in GPB_P_* order
   double* out_user = nullptr;          // optional: the same in the caller-facing order {quad, logdet, bad, g1v, g2v, g1r, g2r}
   double* out_host = nullptr;          // optional: pinned + coherent host copy (GPB_P_* order), polled by the host
+  int max_workers = 0;                 // test seam (gpb_hip_vecchia_set_worker_cap): at most this many worker workgroups, 0 = no cap; the kernel does not read it
 };
 #define GPB_MAX_DIM 10
 

@@ -754,7 +754,7 @@ __device__ __forceinline__ void vecchia_finish(const VecchiaKernelArgs& args, in
 // dispatcher balance (2 rounds 0.893 ms, 4 rounds 0.885 ms, 8 rounds 0.874 ms; profiles/r03_a_*) while the table set-up, the argument
 // loads and the launch of a workgroup are still paid once per ~8 groups.  The occupancy and the CU count are asked once per instantiation and device.
 template <int MT, int COV, bool D3, bool WT>
-static int persistent_grid(const VecchiaKernelArgs& args) {
+static int persistent_grid_uncapped(const VecchiaKernelArgs& args) {
   auto kern = vecchia_point_kernel<MT, COV, D3, GPB_INSTANTIATE_MODE, WT>;
   static int cached_dev = -1, per_dev = 0;
   int dev = 0;
@@ -772,6 +772,12 @@ static int persistent_grid(const VecchiaKernelArgs& args) {
   if (args.ngroups <= slots) return args.ngroups;
   const int trips = (int)((args.ngroups + slots - 1) / slots);
   return (args.ngroups + trips - 1) / trips;
+}
+// args.max_workers (test seam, 0 = no cap): fewer workers than the computation above asks for, so that small cases reach the multi-trip body of the loop
+template <int MT, int COV, bool D3, bool WT>
+static int persistent_grid(const VecchiaKernelArgs& args) {
+  const int workers = persistent_grid_uncapped<MT, COV, D3, WT>(args);
+  return args.max_workers > 0 ? std::min(workers, args.max_workers) : workers;
 }
 template <int MT, bool D3>
 static hipError_t launch_cov(int cov, const VecchiaKernelArgs& args, int nblocks, hipStream_t st) {

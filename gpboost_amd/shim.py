@@ -238,6 +238,18 @@ class VecchiaState(object):
         """-1: default (n >= 32768, from the third evaluation), 0: never, 1: always -- the spatially sorted copy of the records the neighbour gathers read."""
         _shim_call(_lib().gpb_hip_vecchia_set_sorted_gather(self.h, C.c_int(int(mode))))
 
+    def set_nugget_diag(self, nug):
+        """Sample weights of the Gaussian likelihood: nug[i] = 1 / w_i in Vecchia order, the diagonals become var + nug[.] (gpb_hip_vecchia_set_nugget_diag);
+        None goes back to the uniform nugget."""
+        if nug is not None:
+            nug = np.ascontiguousarray(nug, dtype=np.float64)
+            assert nug.shape == (self.n,)
+        _shim_call(_lib().gpb_hip_vecchia_set_nugget_diag(self.h, _p(nug)))
+
+    def set_worker_cap(self, cap):
+        """Test seam: at most `cap` persistent workers per point-kernel launch, 0 = the default grid (gpb_hip_vecchia_set_worker_cap)."""
+        _shim_call(_lib().gpb_hip_vecchia_set_worker_cap(self.h, C.c_int(int(cap))))
+
     def laplace_set_weights(self, w):
         """Sample weights of the non-Gaussian likelihood, in the order of the labels (gpb_hip_vecchia_laplace_set_weights); None removes them."""
         ww = None if w is None else np.ascontiguousarray(w, dtype=np.float64)

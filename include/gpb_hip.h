@@ -106,6 +106,11 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_set_neighbors(gpb_hip_vecchia_t* h, const int
  * n >= 32768 from the third evaluation on a neighbour table (the host sort costs ~0.1 s per million points), 0 never, 1 always.  Not used with sample weights.
  * GPB_VECCHIA_SORTED_GATHER=0 in the environment switches the default off. */
 GPB_HIP_EXPORT int gpb_hip_vecchia_set_sorted_gather(gpb_hip_vecchia_t* h, int mode);
+/* Test entry: at most `cap` persistent worker workgroups per launch of the point kernel (m <= 62, d <= 3), 0 (default) = the grid the library computes itself.
+ * A small cap makes every worker take several groups of 16 points, i.e. small test cases run the multi-trip body of the kernel's loop (the prefetch of the next
+ * trip's neighbour indices, the running sums and the running product behind log|Psi|).  Per-point results (A, D, u) do not depend on it by a bit; sums differ
+ * by the rounding of another summation order.  Not a tuning knob: the default grid is what is measured.  The generality kernel (m > 62 or d > 3) ignores it. */
+GPB_HIP_EXPORT int gpb_hip_vecchia_set_worker_cap(gpb_hip_vecchia_t* h, int32_t cap);
 GPB_HIP_EXPORT int gpb_hip_vecchia_get_neighbors(gpb_hip_vecchia_t* h, int32_t* nn);
 
 /* Multi-GPU: this handle evaluates points [i_begin, i_end) of the ordering only (default: all).

@@ -371,6 +371,7 @@ EXPORT int gpb_hip_vecchia_find_neighbors(gpb_hip_vecchia_t* h, int* has_duplica
   return 0;
 }
 EXPORT int gpb_hip_vecchia_set_neighbors(gpb_hip_vecchia_t* h, const int32_t* nn) { h->nn.assign(nn, nn + (size_t)h->n * h->m); h->has_nn = true; h->has_factor = false; return 0; }
+EXPORT int gpb_hip_vecchia_set_worker_cap(gpb_hip_vecchia_t*, int32_t) { return 0; }      // (a grid size: nothing to restate on the CPU)
 EXPORT int gpb_hip_vecchia_get_neighbors(gpb_hip_vecchia_t* h, int32_t* nn) {
   if (!h->has_nn) return fail("neighbours have not been determined");
   std::copy(h->nn.begin(), h->nn.end(), nn);

@@ -135,7 +135,7 @@ def test_factor_A_D_u_and_yaux_against_oracle(gpb, orc):
         assert t[2] == 0
 
 
-@pytest.mark.parametrize("n,d,m,ct", [(6000, 2, 30, 0), (5000, 3, 40, 2), (4000, 1, 10, 1), (3000, 2, 62, 0)])
+@pytest.mark.parametrize("n,d,m,ct", [(6000, 2, 30, 0), (5000, 3, 40, 2), (4000, 1, 10, 1), (3000, 2, 62, 0), (3000, 3, 20, 1), (2500, 3, 50, 2)])
 def test_spatially_sorted_gather_changes_no_bit(gpb, orc, n, d, m, ct):
     """Round 5: the neighbour gathers of the point kernel read a Morton-sorted copy of the records through a rewritten neighbour table
     (gpb_hip_vecchia_set_sorted_gather; default for n >= 32768 from the third evaluation).  Forced on for these small cases: likelihood terms, gradient
