@@ -167,6 +167,20 @@ static void laplace_state_free(LaplaceState* s) {
 
 namespace {
 
+// device memory of one call: freed on every way out of the scope
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { dev_free(p); p = o.p; o.p = nullptr; } return *this; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { dev_free(p); }
+  hipError_t alloc(size_t count) { return hipMalloc(&p, sizeof(T) * count); }
+  operator T*() const { return p; }
+};
+
 // Dependency levels of the two triangular solves with B = I - A (row i depends on rows nn[i][.] < i) and B^T (row j
 // depends on the rows i > j that have j as a neighbour).  Rows of one level are independent; inside a level they are kept in
 // ascending order (counting sort), so the schedule -- and with it every result -- is deterministic.  Each solve gets its
@@ -707,6 +721,40 @@ double pc_host_cov_grad(int cov, double d, double var, double a) {      // d / d
   if (cov == 1) return -var * r * r * std::exp(-r);
   return -var * r * r * (1.0 + r) / 3.0 * std::exp(-r);
 }
+// Sigma_m of k inducing points (k x 3 row-major) with the jittered diagonal (JITTER_MULT_IP_FITC_FSA = 1 + 1e-6), the inverse of its lower Cholesky factor L_m (row-major) and
+// log|Sigma_m| -- the k x k host part of "fitc" and of the full-scale approximation.  -1: not positive definite
+int ip_cov_factor(const std::vector<double>& ip3, int k, int cov_type, double var, double a, std::vector<double>* Sm_out, std::vector<double>* Li_out, double* logdet) {
+  std::vector<double>& Sm = *Sm_out; std::vector<double>& Li = *Li_out;
+  Sm.assign((size_t)k * k, 0.0); Li.assign((size_t)k * k, 0.0);
+  std::vector<double> Lm((size_t)k * k, 0.0);
+  for (int p = 0; p < k; ++p)
+    for (int q = 0; q <= p; ++q) {
+      double d2 = 0.0; for (int c = 0; c < 3; ++c) { const double t = ip3[(size_t)p * 3 + c] - ip3[(size_t)q * 3 + c]; d2 += t * t; }
+      Sm[(size_t)p * k + q] = Sm[(size_t)q * k + p] = pc_host_cov(cov_type, std::sqrt(d2), var, a);
+    }
+  for (int p = 0; p < k; ++p) Sm[(size_t)p * k + p] *= 1.0 + 1e-6;
+  double ld = 0.0;
+  for (int j = 0; j < k; ++j) {
+    double sd = Sm[(size_t)j * k + j];
+    for (int p = 0; p < j; ++p) sd -= Lm[(size_t)j * k + p] * Lm[(size_t)j * k + p];
+    if (!(sd > 0.0)) return -1;
+    const double l = std::sqrt(sd);
+    Lm[(size_t)j * k + j] = l; ld += std::log(l);
+    for (int i = j + 1; i < k; ++i) {
+      double tv = Sm[(size_t)i * k + j];
+      for (int p = 0; p < j; ++p) tv -= Lm[(size_t)i * k + p] * Lm[(size_t)j * k + p];
+      Lm[(size_t)i * k + j] = tv / l;
+    }
+  }
+  *logdet = 2.0 * ld;
+  for (int c = 0; c < k; ++c)                                 // column c of L_m^-1 by forward substitution
+    for (int i = c; i < k; ++i) {
+      double tv = (i == c) ? 1.0 : 0.0;
+      for (int p = c; p < i; ++p) tv -= Lm[(size_t)i * k + p] * Li[(size_t)p * k + c];
+      Li[(size_t)i * k + c] = tv / Lm[(size_t)i * k + i];
+    }
+  return 0;
+}
 int pc_factor_fitc(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double var, double a, hipStream_t st) {
   const int n = h->n, k = s->pc_nip;
   if (k < 1 || !s->d_pcip) return fail("the fitc preconditioner needs its inducing points (gpb_hip_vecchia_laplace_set_inducing_points)");
@@ -726,37 +774,10 @@ int pc_factor_fitc(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double v
   if (s->pctmp_cap < need) { dev_free(s->d_pctmp); s->pctmp_cap = 0; HIP_OK(hipMalloc(&s->d_pctmp, sizeof(double) * need)); s->pctmp_cap = need; }
   double *Ct = s->d_pctmp, *Vt = Ct + (size_t)n * kq, *Mq = Vt + (size_t)n * kq, *dCt = Mq + (size_t)kq * kq;
   if (want_dC && !s->d_pcdL) HIP_OK(hipMalloc(&s->d_pcdL, sizeof(double) * (size_t)n * k));
-  // Sigma_m, its Cholesky factor, L_m^-T (host: k x k)
-  std::vector<double> Sm((size_t)k * k), Lm((size_t)k * k, 0.0), Li((size_t)k * k, 0.0);
-  for (int p = 0; p < k; ++p)
-    for (int q = 0; q <= p; ++q) {
-      double d2 = 0.0; for (int c = 0; c < 3; ++c) { const double t = s->pc_ip[(size_t)p * 3 + c] - s->pc_ip[(size_t)q * 3 + c]; d2 += t * t; }
-      const double v = pc_host_cov(cov_type, std::sqrt(d2), var, a);
-      Sm[(size_t)p * k + q] = Sm[(size_t)q * k + p] = v;
-    }
-  for (int p = 0; p < k; ++p) Sm[(size_t)p * k + p] *= 1.0 + 1e-6;
-  double ld = 0.0;
-  for (int j = 0; j < k; ++j) {
-    double sd = Sm[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sd -= Lm[(size_t)j * k + p] * Lm[(size_t)j * k + p];
-    if (!(sd > 0.0)) return fail("the covariance matrix of the inducing points of the fitc preconditioner is not positive definite");
-    const double l = std::sqrt(sd);
-    Lm[(size_t)j * k + j] = l; ld += std::log(l);
-    for (int i = j + 1; i < k; ++i) {
-      double tv = Sm[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= Lm[(size_t)i * k + p] * Lm[(size_t)j * k + p];
-      Lm[(size_t)i * k + j] = tv / l;
-    }
-  }
-  for (int c = 0; c < k; ++c)                                 // column c of L_m^-1 by forward substitution
-    for (int i = c; i < k; ++i) {
-      double tv = (i == c) ? 1.0 : 0.0;
-      for (int p = c; p < i; ++p) tv -= Lm[(size_t)i * k + p] * Li[(size_t)p * k + c];
-      Li[(size_t)i * k + c] = tv / Lm[(size_t)i * k + i];
-    }
-  s->pc_Sm = Sm; s->pc_logdet_Sm = 2.0 * ld; s->pc_Linv = Li;
+  if (ip_cov_factor(s->pc_ip, k, cov_type, var, a, &s->pc_Sm, &s->pc_Linv, &s->pc_logdet_Sm))
+    return fail("the covariance matrix of the inducing points of the fitc preconditioner is not positive definite");
   std::vector<double> Mh((size_t)kq * kq, 0.0);              // V = C L_m^-T: M[p][q] = (L_m^-T)[p][q] = (L_m^-1)[q][p]
-  for (int p = 0; p < k; ++p) for (int q = 0; q < k; ++q) Mh[(size_t)p * kq + q] = Li[(size_t)q * k + p];
+  for (int p = 0; p < k; ++p) for (int q = 0; q < k; ++q) Mh[(size_t)p * kq + q] = s->pc_Linv[(size_t)q * k + p];
   HIP_OK(hipMemcpyAsync(Mq, Mh.data(), sizeof(double) * Mh.size(), hipMemcpyHostToDevice, st));
   HIP_OK(gpb::launch_vif_crosscov(cov_type, h->d_pts, s->d_pcip, 0, n, k, kq, h->d, var, a, Ct, want_dC ? dCt : nullptr, st));
   HIP_OK(gpb::launch_vif_gemm(Ct, Mq, n, kq, Vt, false, st));
@@ -797,6 +818,21 @@ int pc_factor_sigma(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double 
   s->pc_cols = mcol;
   return 0;
 }
+// buffers of the factor (A, D, u = B y); one launch of the point kernel in factor mode -- the response slot of pts is not used on these paths (u is discarded)
+int lap_alloc_factor(gpb_hip_vecchia_t* h) {
+  if (h->d_A) return 0;
+  HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)h->n * h->m));
+  HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)h->n));
+  HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)h->n));
+  return 0;
+}
+int lap_launch_factor(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int gauss) {
+  const bool had_y = h->has_y;
+  h->has_y = true;
+  const int rc = vecchia_launch(h, gpb::MODE_FACTOR, cov_type, var, a, gauss, nullptr, 0);
+  h->has_y = had_y;
+  return rc;
+}
 // M = (I_k + L_k^T W L_k)^-1 and its log-determinant for this W (likelihoods.h:16291-16295, :16413-16418): the Gram matrix is reduced on the device, the k x k
 // factorisation runs on the host (Cholesky, then the inverse by k pairs of triangular solves).  *bad = 1: not positive definite / not finite.
 gpb::LapLevels make_levels_vr(const gpb_hip_vecchia_t* h, const LaplaceState* s) {      // the level schedules of B with the entries of A_p
@@ -830,10 +866,7 @@ int pc_refresh_vr(gpb_hip_vecchia_t* h, LaplaceState* s, const double* W, hipStr
   HIP_OK(gpb::pc_vr_nugget(W, s->d_sigma, n, jit, nug, st));
   gpb_hip_vecchia::FactorOverride fo{ s->d_vrA, D2, u2, nug };
   h->factor_override = &fo;
-  const bool had_y = h->has_y;
-  h->has_y = true;
-  const int rc = vecchia_launch(h, gpb::MODE_FACTOR, s->vr_cov, s->vr_var, s->vr_a, 0, nullptr, 0);
-  h->has_y = had_y;
+  const int rc = lap_launch_factor(h, s->vr_cov, s->vr_var, s->vr_a, 0);
   h->factor_override = nullptr;
   if (rc) return -1;
   HIP_OK(gpb::pc_vr_diag(D2, s->d_sigma, n, jit, s->d_vrDs, s->d_vrDs + n, st));
@@ -931,34 +964,7 @@ int vif_lap_factor(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double v
   const int n = h->n, k = h->vif_k, kq = h->vif_kq;
   if ((int)h->vif_ip_host.size() != k * 3) return fail("full-scale Vecchia: the inducing points are not on the host");
   std::vector<double>& Sm = s->vif_Sm; std::vector<double>& Li = s->vif_Linv;
-  Sm.assign((size_t)k * k, 0.0); Li.assign((size_t)k * k, 0.0);
-  std::vector<double> Lm((size_t)k * k, 0.0);
-  for (int p = 0; p < k; ++p)
-    for (int q = 0; q <= p; ++q) {
-      double d2 = 0.0; for (int c = 0; c < 3; ++c) { const double t = h->vif_ip_host[(size_t)p * 3 + c] - h->vif_ip_host[(size_t)q * 3 + c]; d2 += t * t; }
-      Sm[(size_t)p * k + q] = Sm[(size_t)q * k + p] = pc_host_cov(cov_type, std::sqrt(d2), var, a);
-    }
-  for (int p = 0; p < k; ++p) Sm[(size_t)p * k + p] *= 1.0 + 1e-6;            // JITTER_MULT_IP_FITC_FSA
-  double ld = 0.0;
-  for (int j = 0; j < k; ++j) {
-    double sd = Sm[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sd -= Lm[(size_t)j * k + p] * Lm[(size_t)j * k + p];
-    if (!(sd > 0.0)) return fail("the covariance matrix of the inducing points is not positive definite");
-    const double l = std::sqrt(sd);
-    Lm[(size_t)j * k + j] = l; ld += std::log(l);
-    for (int i = j + 1; i < k; ++i) {
-      double tv = Sm[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= Lm[(size_t)i * k + p] * Lm[(size_t)j * k + p];
-      Lm[(size_t)i * k + j] = tv / l;
-    }
-  }
-  s->vif_logdet_Sm = 2.0 * ld;
-  for (int c = 0; c < k; ++c)
-    for (int i = c; i < k; ++i) {
-      double tv = (i == c) ? 1.0 : 0.0;
-      for (int p = c; p < i; ++p) tv -= Lm[(size_t)i * k + p] * Li[(size_t)p * k + c];
-      Li[(size_t)i * k + c] = tv / Lm[(size_t)i * k + i];
-    }
+  if (ip_cov_factor(h->vif_ip_host, k, cov_type, var, a, &Sm, &Li, &s->vif_logdet_Sm)) return fail("the covariance matrix of the inducing points is not positive definite");
   if (vif_upload_matrix(h, 0, Li.data(), true)) return -1;                     // V = C Linv'
   const size_t nkb = sizeof(double) * (size_t)n * kq;
   if (with_grad && !h->d_vdC) { HIP_OK(hipMalloc(&h->d_vdC, nkb)); HIP_OK(hipMalloc(&h->d_vQdC, nkb)); }
@@ -1106,46 +1112,265 @@ double vif_qf_value(const LaplaceState* s, int slot) {
   return r;
 }
 
-// One evaluation of the approximate marginal likelihood (mode finding + log-determinant).  flags & LAP_KEEP_GRAD_STATE: the block CG of
-// the log-determinant also accumulates U (CG_utils.cpp:173) and PI_Z is kept, as the reference does when the gradient may follow.
-int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int num_rand_vec, int seed_rand_vec,
-                 int cg_max_num_it, int cg_max_num_it_tridiag, double cg_delta_conv, double delta_conv_mode_finding,
-                 int flags, double* out9_host, double* mode_host) {
-  const int reset_mode = flags & LAP_RESET_MODE;
-  const bool keep = (flags & LAP_KEEP_GRAD_STATE) != 0;
-  if (!h || !out9_host) return fail("null argument");
-  if (!h->lap || !h->lap->has_y) return fail("labels have not been set (call gpb_hip_vecchia_laplace_set_labels)");
-  if (h->i_begin != 0 || h->i_end != h->n) return fail("the Vecchia-Laplace path needs the whole factor on one device (shard is [%d,%d))", h->i_begin, h->i_end);
-  if (num_rand_vec < 1 || cg_max_num_it < 1 || cg_max_num_it_tridiag < 1) return fail("num_rand_vec, cg_max_num_it and cg_max_num_it_tridiag must be positive");
-  HIP_OK(hipSetDevice(h->device));
-  LaplaceState* s = h->lap;
-  const int n = h->n, m = h->m;
-  hipStream_t st = h->stream;
-  const auto t_start = std::chrono::steady_clock::now();
-  s->grad_state = false; s->gvec_state = false;
-
-  // ---- factor of Sigma^-1 = B^T D^-1 B without nugget (Vecchia_utils.cpp:1599-1609 jitter) ----
-  if (!h->d_A) {
-    HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)n * m));
-    HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)n));
-    HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)n));
+// ---- the workspace map: the ONE place that knows how d_vec / d_blk / d_gvec / d_sc are cut up ------------------------------------------------------
+// Views for t probe vectors (tc columns with the padding of the last chunk of NCB); a buffer that is not allocated yet leaves its views null.  The order of the
+// slots is the order of the lists in lap_work; the sizes the allocations use come from the same struct.
+struct LapWork {
+  static constexpr int kVec = 16, kBlk = 5, kGvec = 6;      // n-vectors of d_vec, block vectors of d_blk, n-vectors of d_gvec
+  static constexpr size_t kParts = 64;                      // partial sums per column and dot product (>= lap_cg_parts(n))
+  int NCB = 4, tch = 0, tc = 0;                             // columns per chunk of the layout [chunk][row][NCB], chunks, columns including the padding
+  size_t nb = 0, vb = 0;                                    // doubles of a block vector, bytes of an n-vector
+  double *mode, *W, *rhs, *dw, *upd, *mnew, *Bm, *dir, *gv, *r, *z, *hh, *v, *t1, *t2, *rdw;      // d_vec (mode finding; W / dw / rdw: the information at the mode afterwards)
+  double *R, *Z, *H, *Vb, *T;                               // d_blk (block CG; free after the log-determinant)
+  double *mprev, *dW3, *dld, *sv, *SdM, *dDs;               // d_gvec: previous mode, third derivatives, d logdet / d mode, implicit solve, SigmaI_deriv mode, dD (storage order)
+  gpb::CgScalars sc1{}, sct{};                              // d_sc: scalars of the single-vector CG; of the block CG (sct.a .. sct.rnorm: 5 tc consecutive doubles, then Td, Ts)
+  gpb::CgScalars sct_plain() const { gpb::CgScalars c = sct; c.Td = c.Ts = nullptr; return c; }      // block CG that records no tridiagonal entries
+  static size_t vec_bytes(int n) { return sizeof(double) * (size_t)n * kVec; }
+  static size_t blk_bytes(int n, int tc) { return sizeof(double) * (size_t)n * tc * kBlk; }
+  static size_t gvec_bytes(int n) { return sizeof(double) * (size_t)n * kGvec; }
+  static size_t sc_doubles(int tc, int p_max) { return (size_t)5 + (size_t)5 * tc + (size_t)2 * tc * p_max + 3 * kParts * ((size_t)tc + 1); }
+};
+template <size_t Want, size_t K>
+void lap_cut(double* base, size_t step, double** const (&slots)[K]) {      // slot i = base + i step, in the order of the list
+  static_assert(K == Want, "the list of slots and the size the buffer is allocated with");
+  for (double** f : slots) { *f = base; if (base) base += step; }
+}
+LapWork lap_work(const gpb_hip_vecchia_t* h, const LaplaceState* s, int t) {
+  LapWork w;
+  const size_t n = (size_t)h->n;
+  w.tch = (t + w.NCB - 1) / w.NCB; w.tc = w.tch * w.NCB;
+  w.nb = n * w.tc; w.vb = sizeof(double) * n;
+  lap_cut<LapWork::kVec>(s->d_vec, n, { &w.mode, &w.W, &w.rhs, &w.dw, &w.upd, &w.mnew, &w.Bm, &w.dir, &w.gv, &w.r, &w.z, &w.hh, &w.v, &w.t1, &w.t2, &w.rdw });
+  lap_cut<LapWork::kBlk>(s->d_blk, w.nb, { &w.R, &w.Z, &w.H, &w.Vb, &w.T });
+  lap_cut<LapWork::kGvec>(s->d_gvec, n, { &w.mprev, &w.dW3, &w.dld, &w.sv, &w.SdM, &w.dDs });
+  if (double* c1 = s->d_sc) {      // [5] single-vector CG, [5 tc] block CG, [tc p_max] + [tc p_max] Lanczos coefficients, per column 2 P partial sums (r.z, h.v) + P (r.r): one column, then tc
+    const size_t tc = (size_t)w.tc, P = LapWork::kParts;
+    double *cb = c1 + 5, *Td = cb + 5 * tc, *Ts = Td + tc * s->p_max, *part = Ts + tc * s->p_max, *partb = part + 3 * P;
+    w.sc1 = gpb::CgScalars{ c1, c1 + 1, c1 + 2, c1 + 3, c1 + 4, nullptr, nullptr, part, part + 2 * P };
+    w.sct = gpb::CgScalars{ cb, cb + tc, cb + 2 * tc, cb + 3 * tc, cb + 4 * tc, Td, Ts, partb, partb + 2 * P * tc };
   }
-  const bool vif = h->vif_k > 0;           // gp_approx = "full_scale_vecchia": Sigma = V V' + B^-1 D B^-T (FindModePostRandEffCalcMLLFSVA, likelihoods.h:3379-3750)
-  if (vif) {
+  return w;
+}
+// a = 1, b = 0 for every column of the block CG (CG_utils.cpp:141-144)
+int lap_cg_reset(const LapWork& w, hipStream_t st) {
+  std::vector<double> init((size_t)5 * w.tc, 0.0);
+  for (int c = 0; c < w.tc; ++c) init[c] = 1.0;
+  HIP_OK(hipMemcpyAsync(w.sct.a, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return 0;
+}
+int lap_fetch(LaplaceState* s, int count, hipStream_t st) {      // d_o[0..count) -> h_o, one sync
+  HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// ---- the three forms of the solves with (Sigma^-1 + W) -------------------------------------------------------------------------------------------
+//   kVadu             (Sigma^-1 + W) x,   P = B' (D^-1 + W) B                                                  ("vadu"; every predictive variance)
+//   kVifSigmaInv      the same with Sigma^-1 = S - Q M^-1 Q' (full-scale Vecchia), P of "vifdu" or the identity ("none")
+//   kWinvPlusSigma    (W^-1 + Sigma) x,   P of pivoted_cholesky / fitc / vecchia_response (Sigma with its low-rank part for full-scale Vecchia)
+enum class LapForm { kVadu, kVifSigmaInv, kWinvPlusSigma };
+LapForm lap_form(const LaplaceState* s) { return s->pc_type == 0 ? LapForm::kVadu : (s->pc_type >= 4 ? LapForm::kVifSigmaInv : LapForm::kWinvPlusSigma); }
+// scratch of the operand's shape: ap for apply, pc for precond, x1 / x2 for the Woodbury parts of either (kVifSigmaInv only)
+struct LapScratch { double *ap, *pc, *x1, *x2; };
+struct LapSolver {
+  gpb_hip_vecchia_t* h; LaplaceState* s; gpb::LapLevels lv; hipStream_t st; int n; LapForm form; bool vif;
+  const double *Ds, *W, *rdw, *Dinv;                       // D (storage order), the information, 1 / (W + 1 / D), 1 / D (full-scale Vecchia)
+  double *vblkA = nullptr, *vblkB = nullptr, *vwdd = nullptr, *vwgt = nullptr;      // kVifSigmaInv: two block vectors and two n-vectors of d_vifblk
+
+  // out = Sigma x = B^-1 D B^-T x (+ V V' x: CG_utils.cpp:267-268, :790-791)
+  int sigma(const double* x, double* out, double* tmp, int ncol, int nc) const {
+    HIP_OK(gpb::lap_vadu(lv, n, Ds, x, out, tmp, ncol, nc, st));
+    if (vif && vif_lowrank_add(s, n, x, out, ncol, nc, st)) return -1;
+    return 0;
+  }
+  // out += -Q M^-1 Q' x (CG_utils.cpp:561-562)
+  int sigI_corr(const double* x, double* out, double* tA, double* tB, int ncol, int nc) const {
+    const int vk = h->vif_k;
+    HIP_OK(gpb::lap_B(lv, n, x, tA, ncol, nc, st));
+    if (vif_small(s, n, vk, ncol, nc)) return -1;
+    HIP_OK(gpb::pc_ltwx(s->d_vifBC, Dinv, s->d_vifMinv, tA, n, vk, ncol, nc, s->d_pcpart, s->d_vifx2, st));        // M^-1 (B C)' D^-1 B x
+    HIP_OK(gpb::pc_combine(s->d_vifBC, Dinv, tA, s->d_vifx2, n, vk, ncol, nc, 3, tA, st));                           // -D^-1 (B C) (.)
+    HIP_OK(gpb::lap_Bt(lv, n, tA, tB, ncol, nc, st));
+    HIP_OK(gpb::lap_lincomb(out, out, tB, 1.0, 1.0, n * ncol * nc, st));
+    return 0;
+  }
+  int apply(const double* x, double* out, const LapScratch& t, int ncol, int nc) const {
+    switch (form) {
+      case LapForm::kVadu:
+      case LapForm::kVifSigmaInv:
+        HIP_OK(gpb::lap_apply(lv, n, Ds, W, x, out, t.ap, ncol, nc, st));
+        return form == LapForm::kVadu ? 0 : sigI_corr(x, out, t.x1, t.x2, ncol, nc);
+      case LapForm::kWinvPlusSigma:                                                  // (CG_utils.cpp:412-418)
+        if (sigma(x, out, t.ap, ncol, nc)) return -1;
+        HIP_OK(gpb::pc_add_div(out, x, W, n, ncol, nc, st));
+        return 0;
+    }
+    return fail("internal: solver form");
+  }
+  // z = P^-1 r
+  int precond(const double* r, double* z, const LapScratch& t, int ncol, int nc) const {
+    switch (form) {
+      case LapForm::kVadu:
+        HIP_OK(gpb::lap_vadu(lv, n, rdw, r, z, t.pc, ncol, nc, st));
+        return 0;
+      case LapForm::kVifSigmaInv:
+        return vif_precond(r, z, t.pc, t.x1, t.x2, ncol, nc);
+      case LapForm::kWinvPlusSigma:
+        return s->pc_type == 3 ? pc_apply_vr(h, s, r, z, ncol, nc, st) : pc_apply(s, n, W, r, z, ncol, nc, 0, st);
+    }
+    return fail("internal: solver form");
+  }
+  // "none" the identity; "vifdu" B^-1 [x + (W + D^-1)^-1 D^-1 B C MM^-1 C' B' D^-1 x], x = (W + D^-1)^-1 B^-T rr (CG_utils.cpp:539-543)
+  int vif_precond(const double* rr, double* zz, double* tt, double* tA, double* tB, int ncol, int nc) const {
+    const int vk = h->vif_k;
+    if (s->pc_type == 5) { HIP_OK(hipMemcpyAsync(zz, rr, sizeof(double) * (size_t)n * ncol * nc, hipMemcpyDeviceToDevice, st)); return 0; }
+    HIP_OK(gpb::lap_vadu(lv, n, rdw, rr, zz, tt, ncol, nc, st));                                               // tt = B^-T rr, zz = B^-1 x
+    HIP_OK(gpb::pc_rowscale(tt, vwdd, n, ncol, nc, 0, tA, st));                                                // D^-1 x
+    HIP_OK(gpb::lap_Bt(lv, n, tA, tB, ncol, nc, st));
+    if (vif_small(s, n, vk, ncol, nc)) return -1;
+    HIP_OK(gpb::pc_ltwx(s->d_vifC, s->d_vifones, s->d_vifMinv + (size_t)vk * vk, tB, n, vk, ncol, nc, s->d_pcpart, s->d_vifx2, st));
+    HIP_OK(gpb::pc_combine(s->d_vifC, s->d_vifones, tB, s->d_vifx2, n, vk, ncol, nc, 3, tA, st));              // -C MM^-1 C' B' D^-1 x
+    HIP_OK(gpb::lap_B(lv, n, tA, tB, ncol, nc, st));
+    HIP_OK(gpb::pc_rowscale(tB, vwdd, n, ncol, nc, 0, tA, st));
+    HIP_OK(gpb::lap_fwd_solve(lv, n, s->d_vifones, tA, tB, ncol, nc, st));
+    HIP_OK(gpb::lap_lincomb(zz, zz, tB, 1.0, -1.0, n * ncol * nc, st));
+    return 0;
+  }
+  // "vifdu" for this W (likelihoods.h:3488-3500): sigma_woodbury_woodbury = M - (D^-1 B C)' diag((W + D^-1)^-1) (D^-1 B C), its inverse to the device
+  int vifdu_refresh(int* pbad) const {
+    const int vk = h->vif_k;
+    *pbad = 0;
+    HIP_OK(gpb::pc_mul3(rdw, Dinv, nullptr, n, vwdd, st));                   // (W + D^-1)^-1 D^-1
+    HIP_OK(gpb::pc_mul3(vwdd, Dinv, nullptr, n, vwgt, st));
+    if (vif_small(s, n, vk, vk, 1)) return -1;                               // (d_vifx2 takes the packed Gram matrix: k (k + 1) / 2 <= k x k doubles)
+    const int npairs = vk * (vk + 1) / 2;
+    std::vector<double> G(npairs), MM((size_t)vk * vk);
+    HIP_OK(gpb::pc_gram(s->d_vifBC, vwgt, n, vk, s->d_pcpart, s->d_vifx2, st));
+    HIP_OK(hipMemcpyAsync(G.data(), s->d_vifx2, sizeof(double) * npairs, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int p = 0; p < vk; ++p) for (int q = 0; q <= p; ++q) MM[(size_t)p * vk + q] = MM[(size_t)q * vk + p] = s->vif_M[(size_t)p * vk + q] - G[(size_t)p * (p + 1) / 2 + q];
+    if (spd_inverse_kk(MM, vk, &s->vif_logdet_MM)) { *pbad = 1; return 0; }
+    HIP_OK(hipMemcpy(s->d_vifMinv + (size_t)vk * vk, MM.data(), sizeof(double) * (size_t)vk * vk, hipMemcpyHostToDevice));
+    return 0;
+  }
+  // the preconditioner of the (W^-1 + Sigma) form for this W
+  int pc_renew(int* pbad, bool for_logdet) const { return s->pc_type == 3 ? pc_refresh_vr(h, s, W, st, pbad, for_logdet) : pc_refresh(s, n, W, st, pbad); }
+};
+LapSolver lap_solver(gpb_hip_vecchia_t* h, LaplaceState* s, const LapWork& w, LapForm form) {
+  const int n = h->n;
+  const bool vif = h->vif_k > 0;
+  LapSolver op{ h, s, make_levels(h, s), h->stream, n, form, vif, s->d_Ds, w.W, w.rdw, vif ? s->d_vifones + n : nullptr };
+  if (form == LapForm::kVifSigmaInv) { op.vblkA = s->d_vifblk; op.vblkB = op.vblkA + w.nb; op.vwdd = op.vblkB + w.nb; op.vwgt = op.vwdd + n; }
+  return op;
+}
+
+// ---- preconditioned CG on a LapSolver from a prepared (X, R, Z, H): Z = P^-1 R, H = Z -------------------------------------------------------------
+// Every step: V = A H -> lap_cg_alpha -> lap_cg_update (X += a H, R -= a V; X may be null) -> the residual norms to h_o + 8 -> test -> Z = P^-1 R -> lap_cg_beta.
+struct LapCgRule {
+  int cap;                  // steps at most
+  double tol;
+  int ncheck;               // the test looks at the norms of this many leading columns ...
+  bool worst;               // ... at their maximum (every column must be below tol), otherwise at their mean
+  int beta_pmax;            // last argument of lap_cg_beta: the stride of the recorded tridiagonal entries (1: nothing recorded)
+  bool stop_after_beta;     // a met tolerance ends the loop after this step's preconditioner + beta (step j of the tridiagonal matrix is recorded), otherwise before them
+};
+enum : int { LAP_CG_ERROR = -1, LAP_CG_CONVERGED = 0, LAP_CG_CAP = 1, LAP_CG_NONFINITE = 2 };
+// *iters: steps whose update ran (stop_after_beta: whose beta ran).  LAP_CG_ERROR: a HIP call or a solve failed, fail() has the message.
+int lap_cg(const LapSolver& op, const LapScratch& scr, double* X, double* R, double* Z, double* H, double* V, int ncol, int nc, const gpb::CgScalars& sc,
+           const LapCgRule& rule, int* iters) {
+  LaplaceState* s = op.s;
+  const int n = op.n;
+  hipStream_t st = op.st;
+  *iters = 0;
+  for (int j = 0; j < rule.cap; ++j) {
+    if (op.apply(H, V, scr, ncol, nc)) return LAP_CG_ERROR;
+    HIP_OK(gpb::lap_cg_alpha(R, Z, H, V, n, ncol, nc, sc, st));
+    HIP_OK(gpb::lap_cg_update(X, R, H, V, n, ncol, nc, sc, st));
+    HIP_OK(hipMemcpyAsync(s->h_o + 8, sc.rnorm, sizeof(double) * (size_t)ncol * nc, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (!rule.stop_after_beta) *iters = j + 1;
+    double norm = 0.0;
+    for (int c = 0; c < rule.ncheck; ++c) {
+      const double rn = s->h_o[8 + c];
+      if (!rule.worst) norm += rn;
+      else if (std::isnan(rn) || std::isinf(rn)) return LAP_CG_NONFINITE;
+      else norm = std::max(norm, rn);
+    }
+    if (!rule.worst) norm /= rule.ncheck;
+    if (std::isnan(norm) || std::isinf(norm)) return LAP_CG_NONFINITE;
+    const bool met = norm < rule.tol;
+    if (!rule.stop_after_beta && (met || j + 1 == rule.cap)) return met ? LAP_CG_CONVERGED : LAP_CG_CAP;
+    if (op.precond(R, Z, scr, ncol, nc)) return LAP_CG_ERROR;
+    HIP_OK(gpb::lap_cg_beta(R, Z, H, n, ncol, nc, sc, j, rule.beta_pmax, st));
+    if (rule.stop_after_beta) { *iters = j + 1; if (met) return LAP_CG_CONVERGED; }
+  }
+  return LAP_CG_CAP;
+}
+
+// ---- one evaluation of the approximate marginal likelihood, in stages -------------------------------------------------------------------------------
+struct LapEvalArgs {
+  int cov_type; double var, a;
+  int t, seed, cg_max_num_it, cg_max_num_it_tridiag;
+  double cg_delta_conv, delta_conv_mode_finding;
+  bool reset_mode, keep;
+};
+// factor of Sigma^-1 = B^T D^-1 B without nugget (Vecchia_utils.cpp:1599-1609 jitter); full-scale Vecchia: of the residual process, with the low-rank parts
+int lap_eval_factor(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e) {
+  hipStream_t st = h->stream;
+  if (lap_alloc_factor(h)) return -1;
+  if (h->vif_k > 0) {       // gp_approx = "full_scale_vecchia": Sigma = V V' + B^-1 D B^-T (FindModePostRandEffCalcMLLFSVA, likelihoods.h:3379-3750)
     if (s->pc_type != 2 && s->pc_type != 4 && s->pc_type != 5) return fail("full-scale Vecchia with a non-Gaussian likelihood: cg_preconditioner_type must be 'fitc' (the reference's default), 'vifdu' or 'none'");
     if (!s->re_ptr.empty()) return fail("full-scale Vecchia with a non-Gaussian likelihood: repeated locations are not on the HIP hot path");
-    if (vif_lap_factor(h, s, cov_type, var, a, keep && s->pc_type == 2, st)) return -1;
-  } else {
-    if (s->pc_type >= 4) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
-    const bool had_y = h->has_y;
-    h->has_y = true;                       // the response slot of pts is not used on this path (u = B y is discarded)
-    const int rc = vecchia_launch(h, gpb::MODE_FACTOR, cov_type, var, a, 0, nullptr, 0);
-    h->has_y = had_y;
-    if (rc) return -1;
-    HIP_OK(hipStreamSynchronize(st));
-    h->has_factor = true;
+    return vif_lap_factor(h, s, e.cov_type, e.var, e.a, e.keep && s->pc_type == 2, st);
   }
-  const double ms_factor = ms_since(t_start);
+  if (s->pc_type >= 4) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
+  if (lap_launch_factor(h, e.cov_type, e.var, e.a, 0)) return -1;
+  HIP_OK(hipStreamSynchronize(st));
+  h->has_factor = true;
+  return 0;
+}
+// log_normalizing_constant_ (part of every LogLikelihood() value, likelihoods.h:11290), per-datum parts weighted, the closed-form parts the reference
+// multiplies by num_data_ not (:10750-10757 Poisson; :10998-11007 gamma, exactly 0 at shape 1; :11019-11030 negative_binomial)
+int laplace_norm_consts(LaplaceState* s, int nd) {
+  const bool hw = !s->weights.empty();
+  if (hw && (int)s->weights.size() != nd) return fail("the sample weights were set for %d data, the data map has %d", (int)s->weights.size(), nd);
+  const double r = s->aux;
+  s->log_norm_const = 0.;
+  auto wt = [&](int i) { return hw ? s->weights[i] : 1.0; };
+  auto binomial_const = [&]() -> int {      // the binomial likelihoods under either link; plain / quasi Bernoulli: 0
+    if (!s->binomial) return 0;
+    if (!hw || !s->real_resp) return fail("binomial likelihoods need the proportions (gpb_hip_vecchia_laplace_set_response_real) and the numbers of trials as sample weights");
+    for (int i = 0; i < nd; ++i) { const double w = s->weights[i], k = w * s->resp_real[i]; s->log_norm_const += std::lgamma(w + 1.) - std::lgamma(k + 1.) - std::lgamma(w - k + 1.); }
+    return 0;
+  };
+  auto weighted_sum_log_y = [&]() { double sl = 0.; for (int i = 0; i < nd; ++i) sl += wt(i) * std::log(s->resp_real[i]); return sl; };
+  const double nu = s->aux2, gauss_const = nd * (0.91893853320467274178 + 0.5 * std::log(r));
+  switch (s->link) {
+    case gpb::kBernoulliLogit: if (binomial_const()) return -1; break;
+    case gpb::kBernoulliProbit: if (binomial_const()) return -1; break;
+    case gpb::kPoisson: for (int i = 0; i < nd; ++i) s->log_norm_const -= wt(i) * std::lgamma((double)s->labels[i] + 1.0); break;     // log(y!): O(1) per observation whatever the count
+    case gpb::kGamma: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = (r == 1.0) ? 0.0 : (r - 1.0) * s->sum_log_y + nd * (r * std::log(r) - std::lgamma(r)); break;
+    case gpb::kNegativeBinomial: {
+      double a1 = 0., slg = 0.;
+      for (int i = 0; i < nd; ++i) { a1 += wt(i) * std::lgamma((double)s->labels[i] + r); slg += wt(i) * std::lgamma((double)s->labels[i] + 1.0); }
+      s->sum_lgamma_y1 = slg;
+      s->log_norm_const = a1 - s->sum_lgamma_y1 + nd * (r * std::log(r) - std::lgamma(r));
+    } break;
+    case gpb::kBeta: s->log_norm_const = nd * std::lgamma(r); break;                                      // likelihoods.h:10866-10868
+    case gpb::kT: s->log_norm_const = nd * (-std::log(r) + std::lgamma((nu + 1.) / 2.) - 0.5 * std::log(nu) - std::lgamma(nu / 2.) - 0.5 * std::log(M_PI)); break;      // :10869-10873 (r = scale, aux2 = df)
+    case gpb::kLogNormal: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = -s->sum_log_y - gauss_const; break;      // :10623-10631, :10887-10889 (r = variance of log y)
+    case gpb::kGaussianLatent: s->log_norm_const = -gauss_const; break;                                   // :10874-10876 (r = error variance)
+    default: return fail("the normalising constant of likelihood id %d is missing", s->link);
+  }
+  s->norm_dirty = false;
+  return 0;
+}
+// what changed since the last evaluation, in the workspace's storage order: data map, response, weights (then the normalising constant), fixed effects; D; the
+// storage-order copies of the full-scale approximation
+int lap_eval_upload(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e) {
+  const int n = h->n;
+  hipStream_t st = h->stream;
   if (!h->has_transpose && build_transpose(h)) return -1;      // fills nn_host
   if (!h->has_levels && build_levels(h, s)) return -1;
   const bool mapped = !s->re_ptr.empty();
@@ -1200,41 +1425,7 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
     HIP_OK(hipMemcpy(s->d_w, ws.data(), sizeof(double) * (size_t)nd, hipMemcpyHostToDevice));
     s->w_dirty = false;
   }
-  if (s->norm_dirty) {
-    // log_normalizing_constant_ (part of every LogLikelihood() value, likelihoods.h:11290), per-datum parts weighted, the closed-form parts the reference
-    // multiplies by num_data_ not (:10750-10757 Poisson; :10998-11007 gamma, exactly 0 at shape 1; :11019-11030 negative_binomial)
-    const bool hw = !s->weights.empty();
-    if (hw && (int)s->weights.size() != nd) return fail("the sample weights were set for %d data, the data map has %d", (int)s->weights.size(), nd);
-    const double r = s->aux;
-    s->log_norm_const = 0.;
-    auto wt = [&](int i) { return hw ? s->weights[i] : 1.0; };
-    auto binomial_const = [&]() -> int {      // the binomial likelihoods under either link; plain / quasi Bernoulli: 0
-      if (!s->binomial) return 0;
-      if (!hw || !s->real_resp) return fail("binomial likelihoods need the proportions (gpb_hip_vecchia_laplace_set_response_real) and the numbers of trials as sample weights");
-      for (int i = 0; i < nd; ++i) { const double w = s->weights[i], k = w * s->resp_real[i]; s->log_norm_const += std::lgamma(w + 1.) - std::lgamma(k + 1.) - std::lgamma(w - k + 1.); }
-      return 0;
-    };
-    auto weighted_sum_log_y = [&]() { double sl = 0.; for (int i = 0; i < nd; ++i) sl += wt(i) * std::log(s->resp_real[i]); return sl; };
-    const double nu = s->aux2, gauss_const = nd * (0.91893853320467274178 + 0.5 * std::log(r));
-    switch (s->link) {
-      case gpb::kBernoulliLogit: if (binomial_const()) return -1; break;
-      case gpb::kBernoulliProbit: if (binomial_const()) return -1; break;
-      case gpb::kPoisson: for (int i = 0; i < nd; ++i) s->log_norm_const -= wt(i) * std::lgamma((double)s->labels[i] + 1.0); break;     // log(y!): O(1) per observation whatever the count
-      case gpb::kGamma: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = (r == 1.0) ? 0.0 : (r - 1.0) * s->sum_log_y + nd * (r * std::log(r) - std::lgamma(r)); break;
-      case gpb::kNegativeBinomial: {
-        double a1 = 0., slg = 0.;
-        for (int i = 0; i < nd; ++i) { a1 += wt(i) * std::lgamma((double)s->labels[i] + r); slg += wt(i) * std::lgamma((double)s->labels[i] + 1.0); }
-        s->sum_lgamma_y1 = slg;
-        s->log_norm_const = a1 - s->sum_lgamma_y1 + nd * (r * std::log(r) - std::lgamma(r));
-      } break;
-      case gpb::kBeta: s->log_norm_const = nd * std::lgamma(r); break;                                      // likelihoods.h:10866-10868
-      case gpb::kT: s->log_norm_const = nd * (-std::log(r) + std::lgamma((nu + 1.) / 2.) - 0.5 * std::log(nu) - std::lgamma(nu / 2.) - 0.5 * std::log(M_PI)); break;      // :10869-10873 (r = scale, aux2 = df)
-      case gpb::kLogNormal: s->sum_log_y = weighted_sum_log_y(); s->log_norm_const = -s->sum_log_y - gauss_const; break;      // :10623-10631, :10887-10889 (r = variance of log y)
-      case gpb::kGaussianLatent: s->log_norm_const = -gauss_const; break;                                   // :10874-10876 (r = error variance)
-      default: return fail("the normalising constant of likelihood id %d is missing", s->link);
-    }
-    s->norm_dirty = false;
-  }
+  if (s->norm_dirty && laplace_norm_consts(s, nd)) return -1;
   if (s->has_fe && s->fe_dirty) {
     if ((int)s->fe.size() != nd) return fail("the fixed effects were set for %d data, the data map has %d", (int)s->fe.size(), nd);
     std::vector<double> fs(nd);
@@ -1245,382 +1436,275 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
   }
   if (!s->d_Ds) HIP_OK(hipMalloc(&s->d_Ds, sizeof(double) * (size_t)n));
   HIP_OK(gpb::lap_scatter(h->d_D, s->d_sigma, n, s->d_Ds, st));
-  const double* Ds = s->d_Ds;
-  if (vif && vif_lap_pack(h, s, keep && s->pc_type == 2, st)) return -1;
-
-  // ---- workspace ----
-  const int t = num_rand_vec;
-  const int NCB = 4;                                   // columns per chunk of the probe block's layout [chunk][row][NCB]
-  const int tch = (t + NCB - 1) / NCB, tc = tch * NCB; // chunks, columns including the padding of the last chunk
-  const int p_max = std::min(cg_max_num_it_tridiag, n);
+  if (h->vif_k > 0 && vif_lap_pack(h, s, e.keep && s->pc_type == 2, st)) return -1;
+  return 0;
+}
+// Probe columns N(0,1) in the layout [chunk][row][NCB]: column c from mt19937(seed_seq{seed, counter, 0, c}) (GenRandVecNormalParallel with run id `counter`), element i
+// of it in row perm[i] (perm = null: row i); the columns padding the last chunk repeat real ones (finite, never read back)
+void lap_draw(int seed, uint32_t counter, int rows, const int* perm, int t, const LapWork& w, double* dst) {
+  std::vector<double> col(rows);
+  for (int c = 0; c < t; ++c) {
+    std::normal_distribution<double> ndist(0.0, 1.0);
+    std::seed_seq seq{ static_cast<uint32_t>(seed), counter, 0u, static_cast<uint32_t>(c) };
+    std::mt19937 gen(seq);
+    for (int i = 0; i < rows; ++i) col[i] = ndist(gen);                 // element i of the reference's column c
+    for (int cc = c; cc < w.tc; cc += t) {
+      double* d = dst + (size_t)(cc / w.NCB) * rows * w.NCB + (cc % w.NCB);
+      for (int i = 0; i < rows; ++i) d[(size_t)(perm ? perm[i] : i) * w.NCB] = col[i];
+    }
+  }
+}
+// workspace of t probe vectors and p_max Lanczos steps; the probes, drawn again when t, the seed or the preconditioner changed
+int lap_eval_workspace(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e) {
+  const int n = h->n, t = e.t;
+  const LapWork w = lap_work(h, s, t);                 // (its sizes; the views are taken once everything is allocated)
+  const int tc = w.tc, p_max = std::min(e.cg_max_num_it_tridiag, n);
   if (!s->d_vec) {      // zero-initialised: padding entries of the solves multiply 0 with whatever sits in x[0]
-    HIP_OK(hipMalloc(&s->d_vec, sizeof(double) * (size_t)n * 16));
-    HIP_OK(hipMemset(s->d_vec, 0, sizeof(double) * (size_t)n * 16));
+    HIP_OK(hipMalloc(&s->d_vec, LapWork::vec_bytes(n)));
+    HIP_OK(hipMemset(s->d_vec, 0, LapWork::vec_bytes(n)));
+  }
+  if (!s->d_gvec) {
+    HIP_OK(hipMalloc(&s->d_gvec, LapWork::gvec_bytes(n)));
+    HIP_OK(hipMemset(s->d_gvec, 0, LapWork::gvec_bytes(n)));
   }
   if (!s->d_o) { HIP_OK(hipMalloc(&s->d_o, sizeof(double) * 8)); }
   if (!s->d_err) {
     HIP_OK(hipMalloc(&s->d_err, sizeof(int)));
     HIP_OK(hipMemset(s->d_err, 0, sizeof(int)));
   }
-  const bool pc = s->pc_type >= 1 && s->pc_type <= 3;      // the (W^-1 + Sigma) form of the solves: pivoted_cholesky (1), fitc (2) or vecchia_response (3)
-  const bool vifdu = s->pc_type == 4, vnone = s->pc_type == 5, vsi = vifdu || vnone;      // full-scale Vecchia, the (Sigma^-1 + W) form with the Woodbury form of Sigma^-1
-  const bool fitc = s->pc_type == 2;
+  const bool vif = h->vif_k > 0;
+  const bool pc = lap_form(s) == LapForm::kWinvPlusSigma;
+  const bool vifdu = s->pc_type == 4, fitc = s->pc_type == 2;
   const bool vr = s->pc_type == 3;                    // no low-rank part: no second set of normals, the probes are drawn with generator counter 0 (likelihoods.h:3993-4009)
-  if (vr) { s->vr_cov = cov_type; s->vr_var = var; s->vr_a = a; }
+  if (vr) { s->vr_cov = e.cov_type; s->vr_var = e.var; s->vr_a = e.a; }
   if (fitc && s->pc_nip < 1) return fail("the fitc preconditioner needs its inducing points (gpb_hip_vecchia_laplace_set_inducing_points)");
   const int pck = fitc ? s->pc_nip : ((pc && !vr) ? std::min(s->pc_rank, n) : (vifdu ? h->vif_k : 0));
-  if (s->t != t || s->p_max != p_max || s->seed != seed_rand_vec || !s->d_rv || s->rv_pc != s->pc_type || s->rv_k != pck) {
+  if (s->t != t || s->p_max != p_max || s->seed != e.seed || !s->d_rv || s->rv_pc != s->pc_type || s->rv_k != pck) {
     dev_free(s->d_rv); dev_free(s->d_blk); dev_free(s->d_sc); dev_free(s->d_pcrv2); dev_free(s->d_vifrv3);
     if (s->h_o) { (void)hipHostFree(s->h_o); s->h_o = nullptr; }
     HIP_OK(hipMalloc(&s->d_rv, sizeof(double) * (size_t)n * tc));
-    HIP_OK(hipMalloc(&s->d_blk, sizeof(double) * (size_t)n * tc * 5));
-    HIP_OK(hipMemset(s->d_blk, 0, sizeof(double) * (size_t)n * tc * 5));
-    HIP_OK(hipMalloc(&s->d_sc, sizeof(double) * ((size_t)5 + (size_t)5 * tc + (size_t)2 * tc * p_max + (size_t)3 * 64 * (tc + 1))));
+    HIP_OK(hipMalloc(&s->d_blk, LapWork::blk_bytes(n, tc)));
+    HIP_OK(hipMemset(s->d_blk, 0, LapWork::blk_bytes(n, tc)));
+    HIP_OK(hipMalloc(&s->d_sc, sizeof(double) * LapWork::sc_doubles(tc, p_max)));
     HIP_OK(hipHostMalloc(&s->h_o, sizeof(double) * (size_t)(8 + tc)));
-    // probes: column c from mt19937(seed_seq{seed, run_id lo, run_id hi, c}), run_id = 0 (first model of the process)
-    // layout [chunk][storage slot][NCB]; the columns padding the last chunk repeat real ones (finite, never read back)
     // pivoted_cholesky: rand_vec_trace_I2_ (k x t) is drawn FIRST (generator counter 0), rand_vec_trace_I_ second (counter 1) -- likelihoods.h:3993-4009
     // (full-scale Vecchia: rand_vec_trace_I2_ (n x t) is drawn FIRST, rand_vec_trace_P_ (k x t) second, likelihoods.h:3633-3652)
-    const uint32_t run_id = (pc && !vr && !vif) ? 1u : 0u;
     if ((pc && !vr) || vifdu) {               // ("vifdu": rand_vec_trace_P_, k x t, generator counter 1, likelihoods.h:3641-3646)
       std::vector<double> rv2((size_t)pck * tc);
-      for (int c = 0; c < t; ++c) {
-        std::normal_distribution<double> ndist(0.0, 1.0);
-        std::seed_seq seq{ static_cast<uint32_t>(seed_rand_vec), vif ? 1u : 0u, 0u, static_cast<uint32_t>(c) };
-        std::mt19937 gen(seq);
-        std::vector<double> col(pck);
-        for (int q = 0; q < pck; ++q) col[q] = ndist(gen);
-        for (int cc = c; cc < tc; cc += t) for (int q = 0; q < pck; ++q) rv2[((size_t)(cc / NCB) * pck + q) * NCB + (cc % NCB)] = col[q];
-      }
+      lap_draw(e.seed, vif ? 1u : 0u, pck, nullptr, t, w, rv2.data());
       HIP_OK(hipMalloc(&s->d_pcrv2, sizeof(double) * (size_t)pck * tc));
       HIP_OK(hipMemcpy(s->d_pcrv2, rv2.data(), sizeof(double) * (size_t)pck * tc, hipMemcpyHostToDevice));
     }
-    std::vector<double> rv((size_t)n * tc), colbuf(n);
-    for (int c = 0; c < t; ++c) {
-      std::normal_distribution<double> ndist(0.0, 1.0);
-      std::seed_seq seq{ static_cast<uint32_t>(seed_rand_vec), run_id, 0u, static_cast<uint32_t>(c) };
-      std::mt19937 gen(seq);
-      for (int i = 0; i < n; ++i) colbuf[i] = ndist(gen);                 // element i of the reference's column c
-      for (int cc = c; cc < tc; cc += t) {
-        double* dst = rv.data() + (size_t)(cc / NCB) * n * NCB + (cc % NCB);
-        for (int i = 0; i < n; ++i) dst[(size_t)s->sigma[i] * NCB] = colbuf[i];
-      }
-    }
+    std::vector<double> rv((size_t)n * tc);
+    lap_draw(e.seed, (pc && !vr && !vif) ? 1u : 0u, n, s->sigma.data(), t, w, rv.data());
     HIP_OK(hipMemcpy(s->d_rv, rv.data(), sizeof(double) * (size_t)n * tc, hipMemcpyHostToDevice));
     if (vifdu) {                               // rand_vec_trace_I3_: generator counter 2
-      for (int c = 0; c < t; ++c) {
-        std::normal_distribution<double> ndist(0.0, 1.0);
-        std::seed_seq seq{ static_cast<uint32_t>(seed_rand_vec), 2u, 0u, static_cast<uint32_t>(c) };
-        std::mt19937 gen(seq);
-        for (int i = 0; i < n; ++i) colbuf[i] = ndist(gen);
-        for (int cc = c; cc < tc; cc += t) {
-          double* dst = rv.data() + (size_t)(cc / NCB) * n * NCB + (cc % NCB);
-          for (int i = 0; i < n; ++i) dst[(size_t)s->sigma[i] * NCB] = colbuf[i];
-        }
-      }
+      lap_draw(e.seed, 2u, n, s->sigma.data(), t, w, rv.data());
       HIP_OK(hipMalloc(&s->d_vifrv3, sizeof(double) * (size_t)n * tc));
       HIP_OK(hipMemcpy(s->d_vifrv3, rv.data(), sizeof(double) * (size_t)n * tc, hipMemcpyHostToDevice));
     }
-    s->t = t; s->p_max = p_max; s->seed = seed_rand_vec; s->rv_pc = s->pc_type; s->rv_k = pck;
+    s->t = t; s->p_max = p_max; s->seed = e.seed; s->rv_pc = s->pc_type; s->rv_k = pck;
   }
-  double* V = s->d_vec;
-  double *mode = V, *W = V + (size_t)n, *rhs = V + (size_t)2 * n, *dw = V + (size_t)3 * n, *upd = V + (size_t)4 * n, *mnew = V + (size_t)5 * n,
-         *Bm = V + (size_t)6 * n, *dir = V + (size_t)7 * n, *gv = V + (size_t)8 * n, *r = V + (size_t)9 * n, *z = V + (size_t)10 * n,
-         *hh = V + (size_t)11 * n, *v = V + (size_t)12 * n, *t1 = V + (size_t)13 * n, *t2 = V + (size_t)14 * n, *rdw = V + (size_t)15 * n;
+  return 0;
+}
+// this evaluation's A in the level-ordered layouts, the inverses of the solves' dense blocks, the covariance part of the low-rank preconditioners; "vifdu" / "none":
+// the scratch of Sigma^-1 = S - Q M^-1 Q' (S = B'D^-1B, Q = S C) and M^-1 on the device
+int lap_eval_operators(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e, const LapWork& w) {
+  const int n = h->n;
+  hipStream_t st = h->stream;
   const gpb::LapLevels lv = make_levels(h, s);
-  for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd })     // this evaluation's A in the level-ordered layouts
+  for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd })
     HIP_OK(gpb::lap_permute_factor(h->d_A, tr->hpos, tr->opos, (size_t)tr->nslots * 32, tr->novf, tr->hent, tr->oent, st));
-  HIP_OK(gpb::lap_dense_build(lv.fdense, h->d_A, st));      // the inverses of the solves' dense blocks for this A
+  HIP_OK(gpb::lap_dense_build(lv.fdense, h->d_A, st));
   HIP_OK(gpb::lap_dense_build(lv.bdense, h->d_A, st));
-  if (pc && !vr && pc_factor_sigma(h, s, cov_type, var, a, st)) return -1;
-  auto pc_renew = [&](const double* Wv, int* pbad, bool for_logdet) -> int { return vr ? pc_refresh_vr(h, s, Wv, st, pbad, for_logdet) : pc_refresh(s, n, Wv, st, pbad); };
-  auto pc_solve = [&](const double* Wv, const double* X, double* out, int ncol_, int nc_) -> int {      // out = P^-1 X
-    return vr ? pc_apply_vr(h, s, X, out, ncol_, nc_, st) : pc_apply(s, n, Wv, X, out, ncol_, nc_, 0, st);
-  };
-  // ---- full-scale Vecchia, "vifdu" / "none": Sigma^-1 = S - Q M^-1 Q' (S = B'D^-1B, Q = S C) applied to vectors; P = B' (W + D^-1) B - Q M^-1 Q' of "vifdu" ----
-  const int vk = h->vif_k;
-  const double* Dinv = vif ? s->d_vifones + n : nullptr;
-  double *vblkA = nullptr, *vblkB = nullptr, *vwdd = nullptr, *vwgt = nullptr;
-  if (vsi) {
-    const size_t need = (size_t)2 * n * tc + (size_t)2 * n;
+  if ((s->pc_type == 1 || s->pc_type == 2) && pc_factor_sigma(h, s, e.cov_type, e.var, e.a, st)) return -1;
+  if (lap_form(s) == LapForm::kVifSigmaInv) {
+    const int vk = h->vif_k;
+    const size_t need = (size_t)2 * w.nb + (size_t)2 * n;      // (LapSolver: vblkA, vblkB, vwdd, vwgt)
     if (s->vifblk_cap < need) { dev_free(s->d_vifblk); s->vifblk_cap = 0; HIP_OK(hipMalloc(&s->d_vifblk, sizeof(double) * need)); s->vifblk_cap = need; }
-    vblkA = s->d_vifblk; vblkB = vblkA + (size_t)n * tc; vwdd = vblkB + (size_t)n * tc; vwgt = vwdd + n;
     if (!s->d_vifMinv) HIP_OK(hipMalloc(&s->d_vifMinv, sizeof(double) * (size_t)2 * vk * vk));
     std::vector<double> Mi(s->vif_M);
     double ldm = 0.0;
     if (spd_inverse_kk(Mi, vk, &ldm)) return fail("the Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
     HIP_OK(hipMemcpy(s->d_vifMinv, Mi.data(), sizeof(double) * (size_t)vk * vk, hipMemcpyHostToDevice));
   }
-  // out += -Q M^-1 Q' x (CG_utils.cpp:561-562): tA, tB blocks of the shape of x (tA may alias a dead temporary)
-  auto sigI_corr = [&](const double* x, double* out, double* tA, double* tB, int ncol_, int nc_) -> int {
-    HIP_OK(gpb::lap_B(lv, n, x, tA, ncol_, nc_, st));
-    if (vif_small(s, n, vk, ncol_, nc_)) return -1;
-    HIP_OK(gpb::pc_ltwx(s->d_vifBC, Dinv, s->d_vifMinv, tA, n, vk, ncol_, nc_, s->d_pcpart, s->d_vifx2, st));        // M^-1 (B C)' D^-1 B x
-    HIP_OK(gpb::pc_combine(s->d_vifBC, Dinv, tA, s->d_vifx2, n, vk, ncol_, nc_, 3, tA, st));                           // -D^-1 (B C) (.)
-    HIP_OK(gpb::lap_Bt(lv, n, tA, tB, ncol_, nc_, st));
-    HIP_OK(gpb::lap_lincomb(out, out, tB, 1.0, 1.0, n * ncol_ * nc_, st));
-    return 0;
-  };
-  // "vifdu" for this W (likelihoods.h:3488-3500): sigma_woodbury_woodbury = M - (D^-1 B C)' diag((W + D^-1)^-1) (D^-1 B C), its inverse to the device
-  auto vifdu_refresh = [&](int* pbad) -> int {
-    *pbad = 0;
-    HIP_OK(gpb::pc_mul3(rdw, Dinv, nullptr, n, vwdd, st));                   // (W + D^-1)^-1 D^-1
-    HIP_OK(gpb::pc_mul3(vwdd, Dinv, nullptr, n, vwgt, st));
-    if (vif_small(s, n, vk, vk, 1)) return -1;                               // (d_vifx2 takes the packed Gram matrix: k (k + 1) / 2 <= k x k doubles)
-    const int npairs = vk * (vk + 1) / 2;
-    std::vector<double> G(npairs), MM((size_t)vk * vk);
-    HIP_OK(gpb::pc_gram(s->d_vifBC, vwgt, n, vk, s->d_pcpart, s->d_vifx2, st));
-    HIP_OK(hipMemcpyAsync(G.data(), s->d_vifx2, sizeof(double) * npairs, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int p = 0; p < vk; ++p) for (int q = 0; q <= p; ++q) MM[(size_t)p * vk + q] = MM[(size_t)q * vk + p] = s->vif_M[(size_t)p * vk + q] - G[(size_t)p * (p + 1) / 2 + q];
-    if (spd_inverse_kk(MM, vk, &s->vif_logdet_MM)) { *pbad = 1; return 0; }
-    HIP_OK(hipMemcpy(s->d_vifMinv + (size_t)vk * vk, MM.data(), sizeof(double) * (size_t)vk * vk, hipMemcpyHostToDevice));
-    return 0;
-  };
-  // zz = P^-1 rr: "none" the identity; "vifdu" B^-1 [x + (W + D^-1)^-1 D^-1 B C MM^-1 C' B' D^-1 x], x = (W + D^-1)^-1 B^-T rr (CG_utils.cpp:539-543).  tt, tA, tB: scratch of rr's shape
-  auto vif_precond = [&](const double* rr, double* zz, double* tt, double* tA, double* tB, int ncol_, int nc_) -> int {
-    if (vnone) { HIP_OK(hipMemcpyAsync(zz, rr, sizeof(double) * (size_t)n * ncol_ * nc_, hipMemcpyDeviceToDevice, st)); return 0; }
-    HIP_OK(gpb::lap_vadu(lv, n, rdw, rr, zz, tt, ncol_, nc_, st));                                               // tt = B^-T rr, zz = B^-1 x
-    HIP_OK(gpb::pc_rowscale(tt, vwdd, n, ncol_, nc_, 0, tA, st));                                                // D^-1 x
-    HIP_OK(gpb::lap_Bt(lv, n, tA, tB, ncol_, nc_, st));
-    if (vif_small(s, n, vk, ncol_, nc_)) return -1;
-    HIP_OK(gpb::pc_ltwx(s->d_vifC, s->d_vifones, s->d_vifMinv + (size_t)vk * vk, tB, n, vk, ncol_, nc_, s->d_pcpart, s->d_vifx2, st));
-    HIP_OK(gpb::pc_combine(s->d_vifC, s->d_vifones, tB, s->d_vifx2, n, vk, ncol_, nc_, 3, tA, st));              // -C MM^-1 C' B' D^-1 x
-    HIP_OK(gpb::lap_B(lv, n, tA, tB, ncol_, nc_, st));
-    HIP_OK(gpb::pc_rowscale(tB, vwdd, n, ncol_, nc_, 0, tA, st));
-    HIP_OK(gpb::lap_fwd_solve(lv, n, s->d_vifones, tA, tB, ncol_, nc_, st));
-    HIP_OK(gpb::lap_lincomb(zz, zz, tB, 1.0, -1.0, n * ncol_ * nc_, st));
-    return 0;
-  };
-  double* scb = s->d_sc + 5;
-  double* scp = scb + (size_t)5 * tc + (size_t)2 * tc * p_max;            // partial dot products: 3 x 64 per column
-  const gpb::CgScalars sc1{ s->d_sc, s->d_sc + 1, s->d_sc + 2, s->d_sc + 3, s->d_sc + 4, nullptr, nullptr, scp, scp + 128 };
-  const gpb::CgScalars sct{ scb, scb + tc, scb + 2 * tc, scb + 3 * tc, scb + 4 * tc, scb + 5 * tc, scb + 5 * tc + (size_t)tc * p_max,
-                            scp + 192, scp + 192 + (size_t)128 * tc };
-  auto fetch = [&](int count) -> int {      // d_o[0..count) -> h_o, one sync
-    HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-  };
-  const size_t vb = sizeof(double) * (size_t)n;
-
-  // ---- mode finding (likelihoods.h:3773-3978) ----
+  return 0;
+}
+// mode finding (likelihoods.h:3773-3978): Newton steps with Armijo backtracking, every step one preconditioned CG solve
+struct LapMode { int it = 0, total_cg = 0; double amll = 0.; bool bad = false; };
+int lap_find_mode(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e, const LapWork& w, const LapSolver& op, LapMode* res) {
+  const int n = h->n;
+  hipStream_t st = h->stream;
+  const size_t vb = w.vb;
+  const gpb::LapLevels& lv = op.lv;
+  const double* Ds = s->d_Ds;
+  const double* fe = s->has_fe ? s->d_fe : nullptr;
+  const bool vif = op.vif, pc = op.form == LapForm::kWinvPlusSigma, vsi = op.form == LapForm::kVifSigmaInv;
+  const LapScratch scr{ w.t1, w.t2, w.dir, w.gv };
   // (gaussian_latent: the objective is quadratic in the mode -- ONE Newton step with ONE trial point, likelihoods.h:473-474)
   const bool one_step = gpb::lik_single_newton_step(s->link);
   const int maxit_mode_newton = one_step ? 1 : 1000, max_lr_shrink = one_step ? 1 : 20;        // :17316, :17322
   const double c_armijo = 1e-4, thr_zero_rhs = 1e-100;            // :17332; ZERO_RHS_CG_THRESHOLD
-  if (reset_mode || !s->has_mode) HIP_OK(hipMemsetAsync(mode, 0, vb, st));
-  if (!s->d_gvec) {
-    HIP_OK(hipMalloc(&s->d_gvec, sizeof(double) * (size_t)n * 6));
-    HIP_OK(hipMemset(s->d_gvec, 0, sizeof(double) * (size_t)n * 6));
-  }
-  HIP_OK(hipMemcpyAsync(s->d_gvec, mode, vb, hipMemcpyDeviceToDevice, st));       // mode_previous_value_ (likelihoods.h:3790-3797)
-  HIP_OK(gpb::lap_B(lv, n, mode, Bm, 1, 1, st));
-  HIP_OK(gpb::lap_objective(s->link, mode, s->resp(), s->has_fe ? s->d_fe : nullptr, Bm, Ds, n, s->d_o, st, s->d_dptr));
-  if (vif && vif_qf_enqueue(s, n, Bm, 0, st)) return -1;
-  if (fetch(2)) return -1;
+  if (e.reset_mode || !s->has_mode) HIP_OK(hipMemsetAsync(w.mode, 0, vb, st));
+  HIP_OK(hipMemcpyAsync(w.mprev, w.mode, vb, hipMemcpyDeviceToDevice, st));       // mode_previous_value_ (likelihoods.h:3790-3797)
+  HIP_OK(gpb::lap_B(lv, n, w.mode, w.Bm, 1, 1, st));
+  HIP_OK(gpb::lap_objective(s->link, w.mode, s->resp(), fe, w.Bm, Ds, n, s->d_o, st, s->d_dptr));
+  if (vif && vif_qf_enqueue(s, n, w.Bm, 0, st)) return -1;
+  if (lap_fetch(s, 2, st)) return -1;
   double amll = s->h_o[0] + s->log_norm_const - 0.5 * (s->h_o[1] - (vif ? vif_qf_value(s, 0) : 0.0)), amll_new = amll;
   int it = 0, total_cg = 0;
   bool bad = false, upd_is_zero = false;
+  const LapCgRule rule{ std::min(e.cg_max_num_it, n), e.cg_delta_conv, 1, false, 1, false };
   for (it = 0; it < maxit_mode_newton; ++it) {
-    HIP_OK(gpb::lap_newton_setup(s->link, mode, s->resp(), s->has_fe ? s->d_fe : nullptr, Ds, n, W, rhs, dw, rdw, st, s->d_dptr));
+    HIP_OK(gpb::lap_newton_setup(s->link, w.mode, s->resp(), fe, Ds, n, w.W, w.rhs, w.dw, w.rdw, st, s->d_dptr));
     // --- CGVecchiaLaplaceVec ---
-    HIP_OK(gpb::lap_dot(rhs, rhs, n, s->d_o, st));
-    if (fetch(2)) return -1;
+    HIP_OK(gpb::lap_dot(w.rhs, w.rhs, n, s->d_o, st));
+    if (lap_fetch(s, 2, st)) return -1;
     int ncg = 0;
     if (s->h_o[1] < thr_zero_rhs) {
-      HIP_OK(hipMemsetAsync(upd, 0, vb, st));
+      HIP_OK(hipMemsetAsync(w.upd, 0, vb, st));
       if (vif) HIP_OK(hipMemsetAsync(s->d_vifu, 0, vb, st));
       upd_is_zero = true;
-    } else if (pc) {
-      // --- CGVecchiaLaplace_Version_SigmaPlusWinvVec (CG_utils.cpp:231-343): (W^-1 + Sigma) u' = Sigma rhs, u = W^-1 u'; preconditioner renewed for this W (likelihoods.h:16282-16295) ---
-      HIP_OK(gpb::pc_wmax(W, n, s->d_o, st));
-      if (fetch(1)) return -1;
-      if (!(s->h_o[0] <= 1e10)) { bad = true; break; }                             // the Woodbury inverse is unstable for a very large information (:16282-16284)
-      int pbad = 0;
-      if (pc_renew(W, &pbad, false)) return -1;
-      if (pbad) { bad = true; break; }
-      HIP_OK(gpb::lap_vadu(lv, n, Ds, rhs, gv, t2, 1, 1, st));                     // Sigma rhs = B^-1 D B^-T rhs (:267-268)
-      if (vif && vif_lowrank_add(s, n, rhs, gv, 1, 1, st)) return -1;              //   + C Sigma_m^-1 C' rhs (likelihoods.h:3535-3538)
-      if (it == 0 || upd_is_zero) {
-        HIP_OK(hipMemsetAsync(upd, 0, vb, st));
-        HIP_OK(hipMemcpyAsync(r, gv, vb, hipMemcpyDeviceToDevice, st));
-      } else if (vif) {                                                             // the iterate is u' of the previous Newton step: r = Sigma rhs - (W^-1 + Sigma) u' (CG_utils.cpp:781-785)
-        HIP_OK(hipMemcpyAsync(upd, s->d_vifu, vb, hipMemcpyDeviceToDevice, st));
-        HIP_OK(gpb::lap_vadu(lv, n, Ds, upd, dir, t2, 1, 1, st));
-        if (vif_lowrank_add(s, n, upd, dir, 1, 1, st)) return -1;
-        HIP_OK(gpb::pc_add_div(dir, upd, W, n, 1, 1, st));
-        HIP_OK(gpb::lap_lincomb(r, gv, dir, 1.0, -1.0, n, st));
-      } else {                                                                      // r = Sigma rhs - u - Sigma W u, the iterate becomes u' = W u (:277-284)
-        HIP_OK(gpb::lap_lincomb(r, gv, upd, 1.0, -1.0, n, st));
-        HIP_OK(gpb::pc_rowscale(upd, W, n, 1, 1, 0, upd, st));
-        HIP_OK(gpb::lap_vadu(lv, n, Ds, upd, dir, t2, 1, 1, st));
-        HIP_OK(gpb::lap_lincomb(r, r, dir, 1.0, -1.0, n, st));
-      }
-      upd_is_zero = false;
-      if (pc_solve(W, r, z, 1, 1)) return -1;
-      HIP_OK(hipMemcpyAsync(hh, z, vb, hipMemcpyDeviceToDevice, st));
-      const int p = std::min(cg_max_num_it, n);
-      for (int j = 0; j < p; ++j) {
-        HIP_OK(gpb::lap_vadu(lv, n, Ds, hh, v, t1, 1, 1, st));
-        if (vif && vif_lowrank_add(s, n, hh, v, 1, 1, st)) return -1;
-        HIP_OK(gpb::pc_add_div(v, hh, W, n, 1, 1, st));                             // v = (W^-1 + Sigma) h
-        HIP_OK(gpb::lap_cg_alpha(r, z, hh, v, n, 1, 1, sc1, st));
-        HIP_OK(gpb::lap_cg_update(upd, r, hh, v, n, 1, 1, sc1, st));
-        HIP_OK(hipMemcpyAsync(s->h_o + 8, sc1.rnorm, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        const double rn = s->h_o[8];
-        ncg = j + 1;
-        if (std::isnan(rn) || std::isinf(rn)) { bad = true; break; }
-        if (rn < cg_delta_conv || (j + 1) == p) {
-          if (vif) HIP_OK(hipMemcpyAsync(s->d_vifu, upd, vb, hipMemcpyDeviceToDevice, st));      // mode_update_part: the next Newton step's start (likelihoods.h:3540-3543)
-          HIP_OK(gpb::pc_rowscale(upd, W, n, 1, 1, 1, upd, st));                                 // u = W^-1 u' (:305-307)
-          break;
-        }
-        if (pc_solve(W, r, z, 1, 1)) return -1;
-        HIP_OK(gpb::lap_cg_beta(r, z, hh, n, 1, 1, sc1, j, 1, st));
-      }
-      if (bad) break;
     } else {
-      upd_is_zero = false;
-      if (vsi) {                                                                    // likelihoods.h:3501-3509
-        HIP_OK(gpb::pc_wmax(W, n, s->d_o, st));
-        if (fetch(1)) return -1;
+      if (pc || vsi) {      // the Woodbury inverses are unstable for a very large information (likelihoods.h:16282-16284, :3501-3509); the preconditioner for this W (:16282-16295)
+        HIP_OK(gpb::pc_wmax(w.W, n, s->d_o, st));
+        if (lap_fetch(s, 1, st)) return -1;
         if (!(s->h_o[0] <= 1e10)) { bad = true; break; }
         int pbad = 0;
-        if (vifdu && vifdu_refresh(&pbad)) return -1;
+        if (pc ? op.pc_renew(&pbad, false) : (s->pc_type == 4 && op.vifdu_refresh(&pbad))) return -1;
         if (pbad) { bad = true; break; }
       }
-      if (it == 0) {
-        HIP_OK(hipMemsetAsync(upd, 0, vb, st));
-        HIP_OK(hipMemcpyAsync(r, rhs, vb, hipMemcpyDeviceToDevice, st));
+      if (pc) {
+        // --- CGVecchiaLaplace_Version_SigmaPlusWinvVec (CG_utils.cpp:231-343): (W^-1 + Sigma) u' = Sigma rhs, u = W^-1 u' ---
+        if (op.sigma(w.rhs, w.gv, w.t2, 1, 1)) return -1;                           // Sigma rhs (:267-268; + C Sigma_m^-1 C' rhs, likelihoods.h:3535-3538)
+        if (it == 0 || upd_is_zero) {
+          HIP_OK(hipMemsetAsync(w.upd, 0, vb, st));
+          HIP_OK(hipMemcpyAsync(w.r, w.gv, vb, hipMemcpyDeviceToDevice, st));
+        } else if (vif) {                                                           // the iterate is u' of the previous Newton step: r = Sigma rhs - (W^-1 + Sigma) u' (CG_utils.cpp:781-785)
+          HIP_OK(hipMemcpyAsync(w.upd, s->d_vifu, vb, hipMemcpyDeviceToDevice, st));
+          if (op.apply(w.upd, w.dir, LapScratch{ w.t2, nullptr, nullptr, nullptr }, 1, 1)) return -1;
+          HIP_OK(gpb::lap_lincomb(w.r, w.gv, w.dir, 1.0, -1.0, n, st));
+        } else {                                                                    // r = Sigma rhs - u - Sigma W u, the iterate becomes u' = W u (:277-284)
+          HIP_OK(gpb::lap_lincomb(w.r, w.gv, w.upd, 1.0, -1.0, n, st));
+          HIP_OK(gpb::pc_rowscale(w.upd, w.W, n, 1, 1, 0, w.upd, st));
+          if (op.sigma(w.upd, w.dir, w.t2, 1, 1)) return -1;
+          HIP_OK(gpb::lap_lincomb(w.r, w.r, w.dir, 1.0, -1.0, n, st));
+        }
+      } else if (it == 0) {
+        HIP_OK(hipMemsetAsync(w.upd, 0, vb, st));
+        HIP_OK(hipMemcpyAsync(w.r, w.rhs, vb, hipMemcpyDeviceToDevice, st));
       } else {
-        HIP_OK(gpb::lap_apply(lv, n, Ds, W, upd, v, t1, 1, 1, st));
-        if (vsi && sigI_corr(upd, v, dir, gv, 1, 1)) return -1;
-        HIP_OK(gpb::lap_lincomb(r, rhs, v, 1.0, -1.0, n, st));
+        if (op.apply(w.upd, w.v, scr, 1, 1)) return -1;
+        HIP_OK(gpb::lap_lincomb(w.r, w.rhs, w.v, 1.0, -1.0, n, st));
       }
-      if (vsi) { if (vif_precond(r, z, t2, dir, gv, 1, 1)) return -1; }
-      else HIP_OK(gpb::lap_vadu(lv, n, rdw, r, z, t2, 1, 1, st));
-      HIP_OK(hipMemcpyAsync(hh, z, vb, hipMemcpyDeviceToDevice, st));
-      const int p = std::min(cg_max_num_it, n);
-      for (int j = 0; j < p; ++j) {
-        HIP_OK(gpb::lap_apply(lv, n, Ds, W, hh, v, t1, 1, 1, st));
-        if (vsi && sigI_corr(hh, v, dir, gv, 1, 1)) return -1;
-        HIP_OK(gpb::lap_cg_alpha(r, z, hh, v, n, 1, 1, sc1, st));
-        HIP_OK(gpb::lap_cg_update(upd, r, hh, v, n, 1, 1, sc1, st));
-        HIP_OK(hipMemcpyAsync(s->h_o + 8, sc1.rnorm, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        const double rn = s->h_o[8];
-        ncg = j + 1;
-        if (std::isnan(rn) || std::isinf(rn)) { bad = true; break; }
-        if (rn < cg_delta_conv) break;
-        if (vsi) { if (vif_precond(r, z, t2, dir, gv, 1, 1)) return -1; }
-        else HIP_OK(gpb::lap_vadu(lv, n, rdw, r, z, t2, 1, 1, st));
-        HIP_OK(gpb::lap_cg_beta(r, z, hh, n, 1, 1, sc1, j, 1, st));
+      upd_is_zero = false;
+      if (op.precond(w.r, w.z, scr, 1, 1)) return -1;
+      HIP_OK(hipMemcpyAsync(w.hh, w.z, vb, hipMemcpyDeviceToDevice, st));
+      const int end = lap_cg(op, scr, w.upd, w.r, w.z, w.hh, w.v, 1, 1, w.sc1, rule, &ncg);
+      if (end == LAP_CG_ERROR) return -1;
+      if (end == LAP_CG_NONFINITE) { bad = true; break; }
+      if (pc) {                                                                     // converged or at the cap
+        if (vif) HIP_OK(hipMemcpyAsync(s->d_vifu, w.upd, vb, hipMemcpyDeviceToDevice, st));      // mode_update_part: the next Newton step's start (likelihoods.h:3540-3543)
+        HIP_OK(gpb::pc_rowscale(w.upd, w.W, n, 1, 1, 1, w.upd, st));                             // u = W^-1 u' (:305-307)
       }
-      if (bad) break;
     }
     total_cg += ncg;
     // --- Armijo backtracking (:3929-3966) ---
-    HIP_OK(gpb::lap_lincomb(dir, upd, mode, 1.0, -1.0, n, st));
-    HIP_OK(gpb::lap_apply(lv, n, Ds, W, dir, gv, t1, 1, 1, st));
-    HIP_OK(gpb::lap_dot(dir, gv, n, s->d_o + 2, st));
+    HIP_OK(gpb::lap_lincomb(w.dir, w.upd, w.mode, 1.0, -1.0, n, st));
+    HIP_OK(gpb::lap_apply(lv, n, Ds, w.W, w.dir, w.gv, w.t1, 1, 1, st));
+    HIP_OK(gpb::lap_dot(w.dir, w.gv, n, s->d_o + 2, st));
     if (vif) {                                                                      // - dir' Q M^-1 Q' dir: the Woodbury part of dir' Sigma^-1 dir (likelihoods.h:3585-3588)
-      HIP_OK(gpb::lap_B(lv, n, dir, t2, 1, 1, st));
-      if (vif_qf_enqueue(s, n, t2, 1, st)) return -1;
+      HIP_OK(gpb::lap_B(lv, n, w.dir, w.t2, 1, 1, st));
+      if (vif_qf_enqueue(s, n, w.t2, 1, st)) return -1;
     }
     double lr = 1.0, gdd = 0.0;
     for (int ih = 0; ih < max_lr_shrink; ++ih) {
-      if (ih == 0) HIP_OK(hipMemcpyAsync(mnew, upd, vb, hipMemcpyDeviceToDevice, st));
-      else HIP_OK(gpb::lap_lincomb(mnew, mode, upd, 1.0 - lr, lr, n, st));
-      HIP_OK(gpb::lap_B(lv, n, mnew, Bm, 1, 1, st));
-      HIP_OK(gpb::lap_objective(s->link, mnew, s->resp(), s->has_fe ? s->d_fe : nullptr, Bm, Ds, n, s->d_o, st, s->d_dptr));
-      if (vif && vif_qf_enqueue(s, n, Bm, 0, st)) return -1;
-      if (fetch(4)) return -1;
+      if (ih == 0) HIP_OK(hipMemcpyAsync(w.mnew, w.upd, vb, hipMemcpyDeviceToDevice, st));
+      else HIP_OK(gpb::lap_lincomb(w.mnew, w.mode, w.upd, 1.0 - lr, lr, n, st));
+      HIP_OK(gpb::lap_B(lv, n, w.mnew, w.Bm, 1, 1, st));
+      HIP_OK(gpb::lap_objective(s->link, w.mnew, s->resp(), fe, w.Bm, Ds, n, s->d_o, st, s->d_dptr));
+      if (vif && vif_qf_enqueue(s, n, w.Bm, 0, st)) return -1;
+      if (lap_fetch(s, 4, st)) return -1;
       gdd = s->h_o[2] - (vif ? vif_qf_value(s, 1) : 0.0);
       amll_new = s->h_o[0] + s->log_norm_const - 0.5 * (s->h_o[1] - (vif ? vif_qf_value(s, 0) : 0.0));
       if (amll_new < (amll + c_armijo * lr * gdd) || std::isnan(amll_new) || std::isinf(amll_new)) lr *= 0.5;
       else break;
     }
-    HIP_OK(hipMemcpyAsync(mode, mnew, vb, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(w.mode, w.mnew, vb, hipMemcpyDeviceToDevice, st));
     // --- CheckConvergenceModeFinding (:16078-16128) ---
     if (std::isnan(amll_new) || std::isinf(amll_new)) { bad = true; break; }
     bool term;
-    if (it == 0) term = std::fabs(amll_new - amll) < delta_conv_mode_finding * std::fabs(amll);
-    else term = (amll_new - amll) < delta_conv_mode_finding * std::fabs(amll);
+    if (it == 0) term = std::fabs(amll_new - amll) < e.delta_conv_mode_finding * std::fabs(amll);
+    else term = (amll_new - amll) < e.delta_conv_mode_finding * std::fabs(amll);
     amll = amll_new;
     if (term) break;
   }
   s->has_mode = !bad;
   HIP_OK(hipStreamSynchronize(st));
-  const double ms_mode = ms_since(t_start);
-  out9_host[1] = it; out9_host[2] = total_cg; out9_host[5] = amll;
-  out9_host[6] = ms_factor; out9_host[7] = ms_mode - ms_factor; out9_host[8] = 0.;
-  if (mode_host) {                       // back to the Vecchia order
-    std::vector<double> ms(n);
-    HIP_OK(hipMemcpyAsync(ms.data(), mode, vb, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) mode_host[i] = ms[s->sigma[i]];
-  }
-  if (bad) {
-    out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = 0;
-    return fail("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");   // likelihoods.h:16100-16103
-  }
-
-  // ---- log|Sigma W + I| by stochastic Lanczos quadrature (:16476-16515) ----
-  const auto t_det = std::chrono::steady_clock::now();
-  const size_t nb = (size_t)n * tc;
-  double *R = s->d_blk, *Z = R + nb, *H = R + 2 * nb, *Vb = R + 3 * nb, *T = R + 4 * nb;
-  HIP_OK(gpb::lap_newton_setup(s->link, mode, s->resp(), s->has_fe ? s->d_fe : nullptr, Ds, n, W, nullptr, dw, rdw, st, s->d_dptr));      // information at the mode (:3981-3984)
+  res->it = it; res->total_cg = total_cg; res->amll = amll; res->bad = bad;
+  return 0;
+}
+// log|Sigma W + I| by stochastic Lanczos quadrature (likelihoods.h:16476-16515) at the mode; out9_host[0], [3], [4]
+int lap_logdet(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e, const LapWork& w, const LapSolver& op, double amll, double* out9_host) {
+  const int n = h->n, t = e.t, tch = w.tch, NCB = w.NCB, tc = w.tc, p_max = s->p_max, vk = h->vif_k;
+  hipStream_t st = h->stream;
+  const size_t nb = w.nb;
+  const gpb::LapLevels& lv = op.lv;
+  const double* Ds = s->d_Ds;
+  const bool vif = op.vif, pc = op.form == LapForm::kWinvPlusSigma, vsi = op.form == LapForm::kVifSigmaInv;
+  const bool fitc = s->pc_type == 2, vr = s->pc_type == 3, vifdu = s->pc_type == 4;
+  double *R = w.R, *Z = w.Z, *H = w.H, *Vb = w.Vb, *T = w.T;
+  const LapScratch scr{ T, T, op.vblkA, op.vblkB };
+  auto lost = [&](int k_done) { out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = k_done; };
+  HIP_OK(gpb::lap_newton_setup(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, Ds, n, w.W, nullptr, w.dw, w.rdw, st, s->d_dptr));      // information at the mode (:3981-3984)
   if (pc) {
     // pivoted_cholesky (:16389-16419): the preconditioner at the information of the mode, probes z_c = L_k r2_c + W^-1/2 r_c with Cov(z_c) = P, Z = P^-1 R
-    HIP_OK(gpb::lap_logsums(Ds, W, n, s->d_o + 4, st));                                     // d_o[5] = sum log W
+    HIP_OK(gpb::lap_logsums(Ds, w.W, n, s->d_o + 4, st));                                   // d_o[5] = sum log W
     int pbad = 0;
     // (full-scale Vecchia: the reference keeps the preconditioner of the LAST NEWTON STEP's information -- diagonal_approx_preconditioner_ / chol_fact_woodbury_preconditioner_ are
     //  renewed inside the Newton loop only, likelihoods.h:3511-3534; the probes :3687 and the log-determinant's terms :16240-16246 use them)
-    if (!vif && pc_renew(W, &pbad, true)) return -1;
+    if (!vif && op.pc_renew(&pbad, true)) return -1;
     if (pbad) {
-      out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = 0;
+      lost(0);
       if (vr) return fail("the Vecchia factor of W^-1 + Sigma is not positive (vecchia_response preconditioner of the log-determinant; zeros or negative values in the information?)");   // likelihoods.h:16389-16397
       return fail("the Cholesky factorisation of I_k + L_k' W L_k failed (pivoted_cholesky preconditioner of the log-determinant)");     // CheckCholeskyFactorization, :16417
     }
     // (fitc: z_c = V r2_c + D^1/2 r_c, :16437;  vecchia_response: z_c = B_p^-1 D_p^1/2 r_c, :16446-16450)
     if (vr) HIP_OK(gpb::lap_fwd_solve(make_levels_vr(h, s), n, s->d_vrDs + n, s->d_rv, R, tch, NCB, st));
-    else HIP_OK(gpb::pc_combine(fitc ? s->d_pcV : s->d_pcL, s->pc_wp(W), s->d_rv, s->d_pcrv2, n, s->pc_k, tch, NCB, 2, R, st));
-    if (pc_solve(W, R, Z, tch, NCB)) return -1;
+    else HIP_OK(gpb::pc_combine(fitc ? s->d_pcV : s->d_pcL, s->pc_wp(w.W), s->d_rv, s->d_pcrv2, n, s->pc_k, tch, NCB, 2, R, st));
   } else if (vsi) {
-    HIP_OK(gpb::lap_logsums(Ds, dw, n, s->d_o + 4, st));
-    if (vnone) HIP_OK(hipMemcpyAsync(R, s->d_rv, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));      // rand_vec_trace_I_ = rand_vec_trace_I2_ (likelihoods.h:3689-3691)
+    HIP_OK(gpb::lap_logsums(Ds, w.dw, n, s->d_o + 4, st));
+    if (!vifdu) HIP_OK(hipMemcpyAsync(R, s->d_rv, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));      // "none": rand_vec_trace_I_ = rand_vec_trace_I2_ (likelihoods.h:3689-3691)
     else {
       // "vifdu": P^1/2 r = B' W^1/2 r_2 + Sigma^-1 (V r_P + B^-1 D^1/2 r_3)  (likelihoods.h:3654-3685); the preconditioner at the information of the mode (:3693-3707)
       int pbad = 0;
-      if (vifdu_refresh(&pbad)) return -1;
-      if (pbad) { out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = 0; return fail("the Cholesky factorisation of the vifdu preconditioner's Woodbury matrix failed (log-determinant)"); }
-      HIP_OK(gpb::lap_scale_probes(s->d_rv, W, n, tch, NCB, T, st));
+      if (op.vifdu_refresh(&pbad)) return -1;
+      if (pbad) { lost(0); return fail("the Cholesky factorisation of the vifdu preconditioner's Woodbury matrix failed (log-determinant)"); }
+      HIP_OK(gpb::lap_scale_probes(s->d_rv, w.W, n, tch, NCB, T, st));
       HIP_OK(gpb::lap_Bt(lv, n, T, R, tch, NCB, st));                                            // B' W^1/2 r_2
       HIP_OK(gpb::lap_scale_probes(s->d_vifrv3, Ds, n, tch, NCB, T, st));
       HIP_OK(gpb::lap_fwd_solve(lv, n, s->d_vifones, T, Vb, tch, NCB, st));                       // B^-1 D^1/2 r_3
       if (vif_small(s, n, vk, tch, NCB)) return -1;
       HIP_OK(gpb::pc_combine(s->d_vifV, s->d_vifones, Vb, s->d_pcrv2, n, vk, tch, NCB, 2, H, st));   // Sigma^1/2 r = V r_P + B^-1 D^1/2 r_3
       HIP_OK(gpb::lap_B(lv, n, H, T, tch, NCB, st));
-      HIP_OK(gpb::pc_rowscale(T, Dinv, n, tch, NCB, 0, T, st));
+      HIP_OK(gpb::pc_rowscale(T, op.Dinv, n, tch, NCB, 0, T, st));
       HIP_OK(gpb::lap_Bt(lv, n, T, Vb, tch, NCB, st));                                           // S Sigma^1/2 r
       HIP_OK(gpb::lap_lincomb(R, R, Vb, 1.0, 1.0, (int)nb, st));
       HIP_OK(gpb::pc_ltwx(s->d_vifC, s->d_vifones, s->d_vifMinv, Vb, n, vk, tch, NCB, s->d_pcpart, s->d_vifx2, st));       // M^-1 C' S Sigma^1/2 r
-      HIP_OK(gpb::pc_combine(s->d_vifBC, Dinv, T, s->d_vifx2, n, vk, tch, NCB, 3, T, st));                                 // -D^-1 B C (.)
+      HIP_OK(gpb::pc_combine(s->d_vifBC, op.Dinv, T, s->d_vifx2, n, vk, tch, NCB, 3, T, st));                              // -D^-1 B C (.)
       HIP_OK(gpb::lap_Bt(lv, n, T, Vb, tch, NCB, st));                                                                    // -Q M^-1 C' S Sigma^1/2 r
       HIP_OK(gpb::lap_lincomb(R, R, Vb, 1.0, 1.0, (int)nb, st));
     }
-    if (vif_precond(R, Z, T, vblkA, vblkB, tch, NCB)) return -1;
   } else {
-  HIP_OK(gpb::lap_logsums(Ds, dw, n, s->d_o + 4, st));
-  HIP_OK(gpb::lap_scale_probes(s->d_rv, dw, n, tch, NCB, T, st));                          // z_c = B^T (D^-1 + W)^0.5 r_c
-  HIP_OK(gpb::lap_Bt(lv, n, T, R, tch, NCB, st));
-  HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
+    HIP_OK(gpb::lap_logsums(Ds, w.dw, n, s->d_o + 4, st));
+    HIP_OK(gpb::lap_scale_probes(s->d_rv, w.dw, n, tch, NCB, T, st));                        // z_c = B^T (D^-1 + W)^0.5 r_c
+    HIP_OK(gpb::lap_Bt(lv, n, T, R, tch, NCB, st));
   }
+  if (op.precond(R, Z, scr, tch, NCB)) return -1;
   HIP_OK(hipMemcpyAsync(H, Z, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+  const bool keep = e.keep && !vr && !vsi;
   double* Ublk = nullptr;
-  if (keep && !vr && !vsi) {
+  if (keep) {
     const size_t gneed = (pc ? 4 : 2) * nb;               // pivoted_cholesky: U, the probes Z, and Sigma U / Sigma W W^-1 P^-1 Z of the gradient
     if (s->gblk_cap < gneed) {
       dev_free(s->d_gblk); s->gblk_cap = 0;
@@ -1631,46 +1715,18 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
     HIP_OK(hipMemsetAsync(Ublk, 0, sizeof(double) * nb, st));
     HIP_OK(hipMemcpyAsync(s->d_gblk + nb, pc ? R : Z, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));     // PI_Z (vadu) / rand_vec_trace_P_ (pivoted_cholesky)
   }
-  {
-    std::vector<double> init((size_t)5 * tc, 0.0);
-    for (int c = 0; c < tc; ++c) init[c] = 1.0;                                     // a = 1, b = 0 (CG_utils.cpp:141-144)
-    HIP_OK(hipMemcpyAsync(scb, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
-  }
+  if (lap_cg_reset(w, st)) return -1;
   int k_done = 0;
-  bool early = false;
-  for (int j = 0; j < p_max; ++j) {
-    if (pc) {                                                                               // V = (W^-1 + Sigma) H (CG_utils.cpp:412-418)
-      HIP_OK(gpb::lap_vadu(lv, n, Ds, H, Vb, T, tch, NCB, st));
-      if (vif && vif_lowrank_add(s, n, H, Vb, tch, NCB, st)) return -1;
-      HIP_OK(gpb::pc_add_div(Vb, H, W, n, tch, NCB, st));
-    } else {
-    HIP_OK(gpb::lap_apply(lv, n, Ds, W, H, Vb, T, tch, NCB, st));
-    if (vsi && sigI_corr(H, Vb, T, vblkA, tch, NCB)) return -1;
-    }
-    HIP_OK(gpb::lap_cg_alpha(R, Z, H, Vb, n, tch, NCB, sct, st));
-    HIP_OK(gpb::lap_cg_update(Ublk, R, H, Vb, n, tch, NCB, sct, st));
-    HIP_OK(hipMemcpyAsync(s->h_o + 8, sct.rnorm, sizeof(double) * tc, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    double mean_norm = 0.0;
-    for (int c = 0; c < t; ++c) mean_norm += s->h_o[8 + c];
-    mean_norm /= t;
-    if (std::isnan(mean_norm) || std::isinf(mean_norm)) { bad = true; break; }
-    if (mean_norm < cg_delta_conv) early = true;
-    if (pc) { if (pc_solve(W, R, Z, tch, NCB)) return -1; }
-    else if (vsi) { if (vif_precond(R, Z, T, vblkA, vblkB, tch, NCB)) return -1; }
-    else HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
-    HIP_OK(gpb::lap_cg_beta(R, Z, H, n, tch, NCB, sct, j, p_max, st));
-    k_done = j + 1;
-    if (early) break;
-  }
-  if (bad) {
-    out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = k_done;
+  // (the mean over the t real columns: the padding columns are not looked at)
+  const int end = lap_cg(op, scr, Ublk, R, Z, H, Vb, tch, NCB, w.sct, LapCgRule{ p_max, e.cg_delta_conv, t, false, p_max, true }, &k_done);
+  if (end == LAP_CG_ERROR) return -1;
+  if (end == LAP_CG_NONFINITE) {
+    lost(k_done);
     return fail("NaN or Inf occurred in the conjugate gradient algorithm (log-determinant)");       // CG_utils.cpp:183-186
   }
   std::vector<double> Tds((size_t)2 * tc * p_max);
-  HIP_OK(hipMemcpyAsync(Tds.data(), sct.Td, sizeof(double) * Tds.size(), hipMemcpyDeviceToHost, st));
-  if (fetch(6)) return -1;
+  HIP_OK(hipMemcpyAsync(Tds.data(), w.sct.Td, sizeof(double) * Tds.size(), hipMemcpyDeviceToHost, st));
+  if (lap_fetch(s, 6, st)) return -1;
   if (lap_check_solves(s, st)) return -1;
   double ldet = 0.0;
   for (int c = 0; c < t; ++c) ldet += tridiag_quadrature_log(Tds.data() + (size_t)c * p_max, Tds.data() + (size_t)tc * p_max + (size_t)c * p_max, k_done);
@@ -1684,8 +1740,52 @@ int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int n
                        : pc ? (ldet + s->h_o[5]) + ((fitc || vr) ? s->pc_logdet : s->pc_logdet - s->h_o[5]) : ldet - s->h_o[4] + s->h_o[5];
   out9_host[0] = amll - 0.5 * log_det;                                              // :4026
   out9_host[3] = log_det; out9_host[4] = k_done;
+  if (keep) { s->grad_state = true; s->g_cov = e.cov_type; s->g_var = e.var; s->g_a = e.a; s->g_t = t; }
+  return 0;
+}
+
+// One evaluation of the approximate marginal likelihood (mode finding + log-determinant).  flags & LAP_KEEP_GRAD_STATE: the block CG of
+// the log-determinant also accumulates U (CG_utils.cpp:173) and PI_Z is kept, as the reference does when the gradient may follow.
+int laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int num_rand_vec, int seed_rand_vec,
+                 int cg_max_num_it, int cg_max_num_it_tridiag, double cg_delta_conv, double delta_conv_mode_finding,
+                 int flags, double* out9_host, double* mode_host) {
+  if (!h || !out9_host) return fail("null argument");
+  if (!h->lap || !h->lap->has_y) return fail("labels have not been set (call gpb_hip_vecchia_laplace_set_labels)");
+  if (h->i_begin != 0 || h->i_end != h->n) return fail("the Vecchia-Laplace path needs the whole factor on one device (shard is [%d,%d))", h->i_begin, h->i_end);
+  if (num_rand_vec < 1 || cg_max_num_it < 1 || cg_max_num_it_tridiag < 1) return fail("num_rand_vec, cg_max_num_it and cg_max_num_it_tridiag must be positive");
+  HIP_OK(hipSetDevice(h->device));
+  LaplaceState* s = h->lap;
+  const int n = h->n;
+  hipStream_t st = h->stream;
+  const LapEvalArgs e{ cov_type, var, a, num_rand_vec, seed_rand_vec, cg_max_num_it, cg_max_num_it_tridiag, cg_delta_conv, delta_conv_mode_finding,
+                       (flags & LAP_RESET_MODE) != 0, (flags & LAP_KEEP_GRAD_STATE) != 0 };
+  const auto t_start = std::chrono::steady_clock::now();
+  s->grad_state = false; s->gvec_state = false;
+  if (lap_eval_factor(h, s, e)) return -1;
+  const double ms_factor = ms_since(t_start);
+  if (lap_eval_upload(h, s, e)) return -1;
+  if (lap_eval_workspace(h, s, e)) return -1;
+  const LapWork w = lap_work(h, s, e.t);
+  if (lap_eval_operators(h, s, e, w)) return -1;
+  const LapSolver op = lap_solver(h, s, w, lap_form(s));
+  LapMode md;
+  if (lap_find_mode(h, s, e, w, op, &md)) return -1;
+  const double ms_mode = ms_since(t_start);
+  out9_host[1] = md.it; out9_host[2] = md.total_cg; out9_host[5] = md.amll;
+  out9_host[6] = ms_factor; out9_host[7] = ms_mode - ms_factor; out9_host[8] = 0.;
+  if (mode_host) {                       // back to the Vecchia order
+    std::vector<double> ms(n);
+    HIP_OK(hipMemcpyAsync(ms.data(), w.mode, w.vb, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) mode_host[i] = ms[s->sigma[i]];
+  }
+  if (md.bad) {
+    out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = 0;
+    return fail("NaN or Inf occurred in the mode finding algorithm for the Laplace approximation");   // likelihoods.h:16100-16103
+  }
+  const auto t_det = std::chrono::steady_clock::now();
+  if (lap_logdet(h, s, e, w, op, md.amll, out9_host)) return -1;
   out9_host[8] = ms_since(t_det);
-  if (keep && !vr && !vsi) { s->grad_state = true; s->g_cov = cov_type; s->g_var = var; s->g_a = a; s->g_t = t; }
   return 0;
 }
 // ---- full-scale Vecchia x non-Gaussian likelihood: the covariance parameters' part of CalcGradNegMargLikelihoodLaplaceApproxFSVA (likelihoods.h:5413-5520), "fitc" preconditioner.
@@ -1957,24 +2057,20 @@ int laplace_grad_current(gpb_hip_vecchia_t* h, int cg_max_num_it, double cg_delt
   if (!s || !s->grad_state || !s->d_gblk) return fail("the gradient needs the state of an evaluation that kept it (gpb_hip_vecchia_laplace_eval with keep_grad_state)");
   if (cg_max_num_it < 1) return fail("cg_max_num_it must be positive");
   HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, m = h->m, t = s->g_t, NCB = 4;
-  const int tch = (t + NCB - 1) / NCB, tc = tch * NCB, p_max = s->p_max;
-  const size_t nb = (size_t)n * tc, vb = sizeof(double) * (size_t)n;
+  const int n = h->n, m = h->m, t = s->g_t;
   hipStream_t st = h->stream;
-  double* V = s->d_vec;
-  double *mode = V, *W = V + (size_t)n, *rhs = V + (size_t)2 * n, *upd = V + (size_t)4 * n, *mnew = V + (size_t)5 * n,
-         *Bm = V + (size_t)6 * n, *dir = V + (size_t)7 * n, *gv = V + (size_t)8 * n, *r = V + (size_t)9 * n, *z = V + (size_t)10 * n,
-         *hh = V + (size_t)11 * n, *v = V + (size_t)12 * n, *t1 = V + (size_t)13 * n, *t2 = V + (size_t)14 * n, *rdw = V + (size_t)15 * n;
-  double *dW3 = s->d_gvec + (size_t)n, *dld = s->d_gvec + (size_t)2 * n, *sv = s->d_gvec + (size_t)3 * n, *SdM = s->d_gvec + (size_t)4 * n,
-         *dDs = s->d_gvec + (size_t)5 * n;
-  double *R = s->d_blk, *Z = R + nb, *H = R + 2 * nb, *Vb = R + 3 * nb, *T = R + 4 * nb;      // free after the log-determinant
+  const LapWork w = lap_work(h, s, t);
+  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
+  const size_t nb = w.nb, vb = w.vb;
+  double *mode = w.mode, *W = w.W, *rhs = w.rhs, *upd = w.upd, *mnew = w.mnew, *Bm = w.Bm, *dir = w.dir, *gv = w.gv, *r = w.r, *z = w.z, *hh = w.hh, *v = w.v,
+         *t1 = w.t1, *t2 = w.t2, *rdw = w.rdw;
+  double *dW3 = w.dW3, *dld = w.dld, *sv = w.sv, *SdM = w.SdM, *dDs = w.dDs;
+  double *R = w.R, *Z = w.Z, *H = w.H, *Vb = w.Vb, *T = w.T;      // free after the log-determinant
   const double *U = s->d_gblk, *PIZ = s->d_gblk + nb;
   const double* Ds = s->d_Ds;
   const double* fe = s->has_fe ? s->d_fe : nullptr;
-  const gpb::LapLevels lv = make_levels(h, s);
-  double* scb = s->d_sc + 5;
-  double* scp = scb + (size_t)5 * tc + (size_t)2 * tc * p_max;
-  const gpb::CgScalars sc1{ s->d_sc, s->d_sc + 1, s->d_sc + 2, s->d_sc + 3, s->d_sc + 4, nullptr, nullptr, scp, scp + 128 };
+  const LapSolver op = lap_solver(h, s, w, lap_form(s));
+  const gpb::LapLevels& lv = op.lv;
   const size_t go_need = (size_t)10 * tc + 6;
   if (s->go_cap < go_need) {
     dev_free(s->d_go);
@@ -2011,44 +2107,19 @@ int laplace_grad_current(gpb_hip_vecchia_t* h, int cg_max_num_it, double cg_delt
   HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   HIP_OK(hipMemsetAsync(sv, 0, vb, st));
-  if (pc && !(s->h_o[1] < 1e-100)) {        // Inv_SigmaI_plus_ZtWZ_Vecchia_iterative_given_PC -> CGVecchiaLaplace_Version_SigmaPlusWinvVec from zero, the preconditioner of the mode
-    HIP_OK(gpb::lap_vadu(lv, n, Ds, rhs, r, t2, 1, 1, st));                         // r = Sigma rhs
-    if (vif && vif_lowrank_add(s, n, rhs, r, 1, 1, st)) return -1;
-    if (pc_apply(s, n, W, r, z, 1, 1, 0, st)) return -1;
-    HIP_OK(hipMemcpyAsync(hh, z, vb, hipMemcpyDeviceToDevice, st));
-    const int p = std::min(cg_max_num_it, n);
-    for (int j = 0; j < p; ++j) {
-      HIP_OK(gpb::lap_vadu(lv, n, Ds, hh, v, t1, 1, 1, st));
-      if (vif && vif_lowrank_add(s, n, hh, v, 1, 1, st)) return -1;
-      HIP_OK(gpb::pc_add_div(v, hh, W, n, 1, 1, st));
-      HIP_OK(gpb::lap_cg_alpha(r, z, hh, v, n, 1, 1, sc1, st));
-      HIP_OK(gpb::lap_cg_update(sv, r, hh, v, n, 1, 1, sc1, st));
-      HIP_OK(hipMemcpyAsync(s->h_o + 8, sc1.rnorm, sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      const double rn = s->h_o[8];
-      if (std::isnan(rn) || std::isinf(rn)) return fail("NaN or Inf occurred in the conjugate gradient algorithm (implicit derivative)");
-      if (rn < cg_delta_conv || (j + 1) == p) { HIP_OK(gpb::pc_rowscale(sv, W, n, 1, 1, 1, sv, st)); break; }
-      if (pc_apply(s, n, W, r, z, 1, 1, 0, st)) return -1;
-      HIP_OK(gpb::lap_cg_beta(r, z, hh, n, 1, 1, sc1, j, 1, st));
-    }
-  } else
   if (!(s->h_o[1] < 1e-100)) {
-    HIP_OK(hipMemcpyAsync(r, rhs, vb, hipMemcpyDeviceToDevice, st));
-    HIP_OK(gpb::lap_vadu(lv, n, rdw, r, z, t2, 1, 1, st));
+    // vadu: CGVecchiaLaplaceVec from zero; otherwise Inv_SigmaI_plus_ZtWZ_Vecchia_iterative_given_PC -> CGVecchiaLaplace_Version_SigmaPlusWinvVec from zero with the
+    // preconditioner of the mode: (W^-1 + Sigma) u' = Sigma rhs, u = W^-1 u'
+    const LapScratch scr{ t1, t2, nullptr, nullptr };
+    if (pc) { if (op.sigma(rhs, r, t2, 1, 1)) return -1; }
+    else HIP_OK(hipMemcpyAsync(r, rhs, vb, hipMemcpyDeviceToDevice, st));
+    if (op.precond(r, z, scr, 1, 1)) return -1;
     HIP_OK(hipMemcpyAsync(hh, z, vb, hipMemcpyDeviceToDevice, st));
-    const int p = std::min(cg_max_num_it, n);
-    for (int j = 0; j < p; ++j) {
-      HIP_OK(gpb::lap_apply(lv, n, Ds, W, hh, v, t1, 1, 1, st));
-      HIP_OK(gpb::lap_cg_alpha(r, z, hh, v, n, 1, 1, sc1, st));
-      HIP_OK(gpb::lap_cg_update(sv, r, hh, v, n, 1, 1, sc1, st));
-      HIP_OK(hipMemcpyAsync(s->h_o + 8, sc1.rnorm, sizeof(double), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      const double rn = s->h_o[8];
-      if (std::isnan(rn) || std::isinf(rn)) return fail("NaN or Inf occurred in the conjugate gradient algorithm (implicit derivative)");
-      if (rn < cg_delta_conv) break;
-      HIP_OK(gpb::lap_vadu(lv, n, rdw, r, z, t2, 1, 1, st));
-      HIP_OK(gpb::lap_cg_beta(r, z, hh, n, 1, 1, sc1, j, 1, st));
-    }
+    int ncg = 0;
+    const int end = lap_cg(op, scr, sv, r, z, hh, v, 1, 1, w.sc1, LapCgRule{ std::min(cg_max_num_it, n), cg_delta_conv, 1, false, 1, false }, &ncg);
+    if (end == LAP_CG_ERROR) return -1;
+    if (end == LAP_CG_NONFINITE) return fail("NaN or Inf occurred in the conjugate gradient algorithm (implicit derivative)");
+    if (pc) HIP_OK(gpb::pc_rowscale(sv, W, n, 1, 1, 1, sv, st));
   }
   // ---- dA, dD wrt the log range; their entries in the two level-ordered layouts ----
   if (!s->d_dA) {
@@ -2195,6 +2266,22 @@ int laplace_grad_current(gpb_hip_vecchia_t* h, int cg_max_num_it, double cg_delt
   }
   return 0;
 }
+// One block solve of the predictive variances: X += (Sigma^-1 + W)^-1 R for the right-hand sides in w.R by preconditioned CG ('vadu', the solver of the mode finding), the cnt
+// leading columns iterated until each residual norm is below tol; the tridiagonal entries are not recorded.  *total_it grows by the steps taken.
+int lap_pred_solve(const LapSolver& op, const LapWork& w, double* X, int cnt, int cg_max_num_it, double tol, const char* what, int* total_it) {
+  const LapScratch scr{ w.T, w.T, nullptr, nullptr };
+  if (op.precond(w.R, w.Z, scr, w.tch, w.NCB)) return -1;
+  HIP_OK(hipMemcpyAsync(w.H, w.Z, sizeof(double) * w.nb, hipMemcpyDeviceToDevice, op.st));
+  if (lap_cg_reset(w, op.st)) return -1;
+  const int p = std::min(cg_max_num_it, op.n);
+  int it = 0;
+  const int end = lap_cg(op, scr, X, w.R, w.Z, w.H, w.Vb, w.tch, w.NCB, w.sct_plain(), LapCgRule{ p, tol, cnt, true, 1, false }, &it);
+  *total_it += it;
+  if (end == LAP_CG_ERROR) return -1;
+  if (end == LAP_CG_NONFINITE) return fail("NaN or Inf occurred in the conjugate gradient algorithm (%s)", what);
+  if (end == LAP_CG_CAP) return fail("the conjugate gradient algorithm of the predictive variances has not converged after %d iterations (residual norm above %g)", p, tol);
+  return 0;
+}
 // Quadratic forms b_p' (Sigma^-1 + W)^-1 b_q of the rows b_p = -A_p of Bpo (prediction points conditioning on observed points) at the state the
 // last laplace_eval left behind -- the mode, W / rdw at the mode, this factor in the level-ordered layouts: the part of the predictive (co)variance
 // of the latent process that PredictLaplaceApproxVecchia (likelihoods.h:8563-8824) adds to Dp.  The reference's "cholesky" branch computes it
@@ -2208,14 +2295,11 @@ int laplace_pred_quad(gpb_hip_vecchia_t* h, int n_pred, int m, const int* nn_p, 
   LaplaceState* s = h->lap;
   if (!s || !s->has_mode || !s->d_blk || !s->d_vec || !s->d_sc) return fail("predictive variances need the state of a likelihood evaluation (mode, information, factor)");
   HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, t = s->t, NCB = 4;
-  const int tch = (t + NCB - 1) / NCB, tc = tch * NCB, p_max = s->p_max;
-  const size_t nb = (size_t)n * tc;
+  const int n = h->n;
   hipStream_t st = h->stream;
-  double* V = s->d_vec;
-  const double *W = V + (size_t)n, *rdw = V + (size_t)15 * n;
-  const double* Ds = s->d_Ds;
-  double *R = s->d_blk, *Z = R + nb, *H = R + 2 * nb, *Vb = R + 3 * nb, *T = R + 4 * nb;
+  const LapWork w = lap_work(h, s, s->t);
+  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
+  const size_t nb = w.nb;
   if (s->gblk_cap < nb) {
     dev_free(s->d_gblk); s->gblk_cap = 0;
     HIP_OK(hipMalloc(&s->d_gblk, sizeof(double) * 2 * nb));
@@ -2223,46 +2307,18 @@ int laplace_pred_quad(gpb_hip_vecchia_t* h, int n_pred, int m, const int* nn_p, 
   }
   s->grad_state = false; s->gvec_state = false;          // U / PI_Z of the log-determinant are overwritten
   double* X = s->d_gblk;
-  const gpb::LapLevels lv = make_levels(h, s);
-  double* scb = s->d_sc + 5;
-  double* scp = scb + (size_t)5 * tc + (size_t)2 * tc * p_max;
-  const gpb::CgScalars sct{ scb, scb + tc, scb + 2 * tc, scb + 3 * tc, scb + 4 * tc, nullptr, nullptr, scp + 192, scp + 192 + (size_t)128 * tc };
+  const LapSolver op = lap_solver(h, s, w, LapForm::kVadu);
   const size_t out_cap = want_cov ? (size_t)n_pred * tc : (size_t)tc;
-  double* d_out = nullptr;
-  HIP_OK(hipMalloc(&d_out, sizeof(double) * out_cap));
-  struct Free { double* p; ~Free() { if (p) (void)hipFree(p); } } guard{ d_out };
-  std::vector<double> out(out_cap), init((size_t)5 * tc, 0.0);
-  for (int c = 0; c < tc; ++c) init[c] = 1.0;
+  DevBuf<double> d_out;
+  HIP_OK(d_out.alloc(out_cap));
+  std::vector<double> out(out_cap);
   int total_it = 0;
   for (int p0 = 0; p0 < n_pred; p0 += tc) {
     const int cnt = std::min(tc, n_pred - p0);
-    HIP_OK(hipMemsetAsync(R, 0, sizeof(double) * nb, st));
+    HIP_OK(hipMemsetAsync(w.R, 0, sizeof(double) * nb, st));
     HIP_OK(hipMemsetAsync(X, 0, sizeof(double) * nb, st));
-    HIP_OK(gpb::lap_pred_rhs(nn_p, A_p, s->d_sigma, n, m, p0, cnt, tch, NCB, R, st));
-    HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
-    HIP_OK(hipMemcpyAsync(H, Z, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(scb, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
-    bool done = false;
-    const int p = std::min(cg_max_num_it, n);
-    for (int j = 0; j < p; ++j) {
-      HIP_OK(gpb::lap_apply(lv, n, Ds, W, H, Vb, T, tch, NCB, st));
-      HIP_OK(gpb::lap_cg_alpha(R, Z, H, Vb, n, tch, NCB, sct, st));
-      HIP_OK(gpb::lap_cg_update(X, R, H, Vb, n, tch, NCB, sct, st));
-      HIP_OK(hipMemcpyAsync(s->h_o + 8, sct.rnorm, sizeof(double) * tc, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      ++total_it;
-      double worst = 0.0;
-      for (int c = 0; c < cnt; ++c) {
-        const double rn = s->h_o[8 + c];
-        if (std::isnan(rn) || std::isinf(rn)) return fail("NaN or Inf occurred in the conjugate gradient algorithm (predictive variances)");
-        worst = std::max(worst, rn);
-      }
-      if (worst < tol) { done = true; break; }
-      HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
-      HIP_OK(gpb::lap_cg_beta(R, Z, H, n, tch, NCB, sct, j, 1, st));
-    }
-    if (!done) return fail("the conjugate gradient algorithm of the predictive variances has not converged after %d iterations (residual norm above %g)", p, tol);
+    HIP_OK(gpb::lap_pred_rhs(nn_p, A_p, s->d_sigma, n, m, p0, cnt, tch, NCB, w.R, st));
+    if (lap_pred_solve(op, w, X, cnt, cg_max_num_it, tol, "predictive variances", &total_it)) return -1;
     if (want_cov) {
       HIP_OK(gpb::lap_pred_quad(nn_p, A_p, s->d_sigma, X, n, m, 0, n_pred, cnt, NCB, 0, d_out, st));
       HIP_OK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)n_pred * cnt, hipMemcpyDeviceToHost, st));
@@ -2295,14 +2351,14 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   if (h->vif_k < 1) return fail("gpb_hip_vecchia_vif_laplace_predict: the handle has no inducing points (full-scale Vecchia models only)");
   if (!s || !s->has_mode || !s->d_vec || !s->d_blk || !s->d_sc || !h->has_factor) return fail("predictions need the state of a likelihood evaluation (mode, information, factor)");
   HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, k = h->vif_k, kq = h->vif_kq, NCB = 4;
+  const int n = h->n, k = h->vif_k, kq = h->vif_kq;
   hipStream_t st = h->stream;
-  const int t = s->t, tch = (t + NCB - 1) / NCB, tc = tch * NCB, p_max = s->p_max;
-  const size_t nb = (size_t)n * tc, vb = sizeof(double) * (size_t)n;
-  double* V = s->d_vec;
-  double *mode = V, *W = V + (size_t)n, *Bm = V + (size_t)6 * n, *dir = V + (size_t)7 * n, *rdw = V + (size_t)15 * n;
-  const double* Ds = s->d_Ds;
-  const gpb::LapLevels lv = make_levels(h, s);
+  const LapWork w = lap_work(h, s, s->t);
+  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
+  const size_t nb = w.nb, vb = w.vb;
+  double *mode = w.mode, *W = w.W, *Bm = w.Bm, *dir = w.dir;
+  const LapSolver op = lap_solver(h, s, w, LapForm::kVadu);
+  const gpb::LapLevels& lv = op.lv;
   s->grad_state = false; s->gvec_state = false;
   if (!s->d_vifC) { HIP_OK(hipMalloc(&s->d_vifC, sizeof(double) * (size_t)n * k)); }
   HIP_OK(gpb::pc_pack_rows(h->d_vC, kq, s->d_sigma, n, k, s->d_vifC, nullptr, st));
@@ -2330,7 +2386,7 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   int m = 0;
   if (cond_all && n_pred > 5000) return fail("full-scale Vecchia prediction, 'latent_order_obs_first_cond_all': %d > 5000 prediction points (dense B_p^-1)", n_pred);
   const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, cond_all, cov_type, var, a, &tp, &m, has_duplicates, 0, false, false, false);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{tp};
+  const auto free_tp = scope_exit([&] { if (tp) gpb_hip_vecchia_free(tp); });
   if (rc) return -1;
   const int n_obs = n, n_all = n_obs + n_pred;
   std::vector<double> ipc((size_t)k * h->d);
@@ -2362,9 +2418,7 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   const int* nn_p = tp->d_nn + (size_t)n_obs * m;
   const double* A_p = tp->d_A + (size_t)n_obs * m;
   int mrow = m;
-  int* d_cols = nullptr; double* d_negv = nullptr;
-  struct FreeI { int* p; ~FreeI() { if (p) (void)hipFree(p); } } gfi{ nullptr };
-  struct FreeD2 { double* p; ~FreeD2() { if (p) (void)hipFree(p); } } gfd{ nullptr };
+  DevBuf<int> d_cols; DevBuf<double> d_negv;
   std::vector<double> Rm;                                  // rows of B_p^-1 ('cond_all')
   std::vector<double> xmean(up);                           // B_p^-1 (B_po s)
   if (cond_all) {
@@ -2409,8 +2463,8 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
     std::vector<int32_t> cols((size_t)n_pred * mmax, -1);
     std::vector<double> negv((size_t)n_pred * mmax, 0.0);
     for (int r = 0; r < n_pred; ++r) for (size_t e = 0; e < Crow[r].size(); ++e) { cols[(size_t)r * mmax + e] = Crow[r][e].first; negv[(size_t)r * mmax + e] = -Crow[r][e].second; }     // (the kernels take A with b = -A)
-    HIP_OK(hipMalloc(&d_cols, sizeof(int) * cols.size())); gfi.p = d_cols;
-    HIP_OK(hipMalloc(&d_negv, sizeof(double) * negv.size())); gfd.p = d_negv;
+    HIP_OK(d_cols.alloc(cols.size()));
+    HIP_OK(d_negv.alloc(negv.size()));
     HIP_OK(hipMemcpy(d_cols, cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_negv, negv.data(), sizeof(double) * negv.size(), hipMemcpyHostToDevice));
     nn_p = d_cols; A_p = d_negv;
@@ -2429,51 +2483,20 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   int it1 = 0;
   if (laplace_pred_quad(h, n_pred, m_rows, nn_p, A_p, cg_max_num_it, tol, want_cov, qd.data(), &it1)) return -1;
   // ---- X = K^-1 W C in blocks of tc columns: G2 = C' W (C - X), M3 = Bpo X ----
-  double *R = s->d_blk, *Z = R + nb, *H = R + 2 * nb, *Vb = R + 3 * nb, *T = R + 4 * nb;
-  if (s->gblk_cap < nb) { dev_free(s->d_gblk); s->gblk_cap = 0; HIP_OK(hipMalloc(&s->d_gblk, sizeof(double) * 2 * nb)); s->gblk_cap = 2 * nb; }
-  double* X = s->d_gblk;
-  double* scb = s->d_sc + 5;
-  double* scp = scb + (size_t)5 * tc + (size_t)2 * tc * p_max;
-  const gpb::CgScalars sct{ scb, scb + tc, scb + 2 * tc, scb + 3 * tc, scb + 4 * tc, nullptr, nullptr, scp + 192, scp + 192 + (size_t)128 * tc };
-  std::vector<double> init((size_t)5 * tc, 0.0);
-  for (int c = 0; c < tc; ++c) init[c] = 1.0;
+  double* X = s->d_gblk;                                   // (sized by laplace_pred_quad)
   if (vif_small(s, n, k, std::max(tch, k), NCB)) return -1;
   std::vector<double> G2((size_t)k * k), M3((size_t)n_pred * k), blk((size_t)tch * k * NCB), outp((size_t)n_pred * tc), Gc(k * (k + 1) / 2);
-  double* d_outp = nullptr;
-  HIP_OK(hipMalloc(&d_outp, sizeof(double) * (size_t)n_pred * tc));
-  struct Free { double* p; ~Free() { if (p) (void)hipFree(p); } } guard2{ d_outp };
+  DevBuf<double> d_outp;
+  HIP_OK(d_outp.alloc((size_t)n_pred * tc));
   HIP_OK(gpb::pc_gram(s->d_vifC, W, n, k, s->d_pcpart, s->d_vifx2, st));                               // C' W C
   HIP_OK(hipMemcpyAsync(Gc.data(), s->d_vifx2, sizeof(double) * Gc.size(), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   int total_it = it1;
   for (int col0 = 0; col0 < k; col0 += tc) {
     const int cnt = std::min(tc, k - col0);
-    HIP_OK(gpb::pc_cols_to_block(s->d_vifC, W, n, k, col0, cnt, tch, NCB, R, st));
+    HIP_OK(gpb::pc_cols_to_block(s->d_vifC, W, n, k, col0, cnt, tch, NCB, w.R, st));
     HIP_OK(hipMemsetAsync(X, 0, sizeof(double) * nb, st));
-    HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
-    HIP_OK(hipMemcpyAsync(H, Z, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    HIP_OK(hipMemcpyAsync(scb, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
-    bool done = false;
-    const int p = std::min(cg_max_num_it, n);
-    for (int j = 0; j < p; ++j) {
-      HIP_OK(gpb::lap_apply(lv, n, Ds, W, H, Vb, T, tch, NCB, st));
-      HIP_OK(gpb::lap_cg_alpha(R, Z, H, Vb, n, tch, NCB, sct, st));
-      HIP_OK(gpb::lap_cg_update(X, R, H, Vb, n, tch, NCB, sct, st));
-      HIP_OK(hipMemcpyAsync(s->h_o + 8, sct.rnorm, sizeof(double) * tc, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      ++total_it;
-      double worst = 0.0;
-      for (int c = 0; c < cnt; ++c) {
-        const double rn = s->h_o[8 + c];
-        if (std::isnan(rn) || std::isinf(rn)) return fail("NaN or Inf occurred in the conjugate gradient algorithm (predictive variances, full-scale Vecchia)");
-        worst = std::max(worst, rn);
-      }
-      if (worst < tol) { done = true; break; }
-      HIP_OK(gpb::lap_vadu(lv, n, rdw, R, Z, T, tch, NCB, st));
-      HIP_OK(gpb::lap_cg_beta(R, Z, H, n, tch, NCB, sct, j, 1, st));
-    }
-    if (!done) return fail("the conjugate gradient algorithm of the predictive variances has not converged after %d iterations (residual norm above %g)", p, tol);
+    if (lap_pred_solve(op, w, X, cnt, cg_max_num_it, tol, "predictive variances, full-scale Vecchia", &total_it)) return -1;
     HIP_OK(gpb::pc_ltwx(s->d_vifC, W, s->d_vifI + (size_t)k * k, X, n, k, tch, NCB, s->d_pcpart, s->d_vifx2, st));      // C' W X
     HIP_OK(hipMemcpyAsync(blk.data(), s->d_vifx2, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, st));
     HIP_OK(gpb::lap_pred_quad(nn_p, A_p, s->d_sigma, X, n, m_rows, 0, n_pred, cnt, NCB, 0, d_outp, st));                   // Bpo X (or B_p^-1 Bpo X)
@@ -2544,7 +2567,7 @@ int gpb_hip_vecchia_laplace_predict(gpb_hip_vecchia_t* h, int32_t n_pred, const 
   gpb_hip_vecchia_t* t = nullptr;
   int m = 0;
   const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, false, cov_type, var, a, &t, &m, has_duplicates, 0);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
+  const auto free_t = scope_exit([&] { if (t) gpb_hip_vecchia_free(t); });
   if (rc) return -1;
   const int n_obs = h->n;
   std::vector<double> u(n_pred), Dp(n_pred);
@@ -2589,11 +2612,9 @@ int gpb_hip_vecchia_laplace_quad_forms(gpb_hip_vecchia_t* h, int32_t n_rows, int
   for (size_t k = 0; k < cnt; ++k) if (cols_host[k] >= h->n) return fail("gpb_hip_vecchia_laplace_quad_forms: column %d of a handle with %d points", cols_host[k], h->n);
   std::vector<double> neg(cnt);
   for (size_t k = 0; k < cnt; ++k) neg[k] = -vals_host[k];                      // the kernels take A_p with b_p = -A_p
-  int* d_cols = nullptr; double* d_neg = nullptr;
-  HIP_OK(hipMalloc(&d_cols, sizeof(int) * cnt));
-  struct FreeI { int* p; ~FreeI() { if (p) (void)hipFree(p); } } g1{ d_cols };
-  HIP_OK(hipMalloc(&d_neg, sizeof(double) * cnt));
-  struct FreeD { double* p; ~FreeD() { if (p) (void)hipFree(p); } } g2{ d_neg };
+  DevBuf<int> d_cols; DevBuf<double> d_neg;
+  HIP_OK(d_cols.alloc(cnt));
+  HIP_OK(d_neg.alloc(cnt));
   HIP_OK(hipMemcpy(d_cols, cols_host, sizeof(int) * cnt, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(d_neg, neg.data(), sizeof(double) * cnt, hipMemcpyHostToDevice));
   if (laplace_pred_quad(h, n_rows, mmax, d_cols, d_neg, cg_max_num_it, tol, want_cov != 0, out_host, cg_iterations)) return -1;
@@ -2617,11 +2638,9 @@ int gpb_hip_vecchia_laplace_mode_var(gpb_hip_vecchia_t* h, int cg_max_num_it, do
   std::vector<int> idx(n);
   std::iota(idx.begin(), idx.end(), 0);
   std::vector<double> minus_one((size_t)n, -1.0);                // b_i = -A_i = e_i
-  int* d_idx = nullptr; double* d_coef = nullptr;
-  HIP_OK(hipMalloc(&d_idx, sizeof(int) * (size_t)n));
-  struct FreeI { int* p; ~FreeI() { if (p) (void)hipFree(p); } } g1{ d_idx };
-  HIP_OK(hipMalloc(&d_coef, sizeof(double) * (size_t)n));
-  struct FreeD { double* p; ~FreeD() { if (p) (void)hipFree(p); } } g2{ d_coef };
+  DevBuf<int> d_idx; DevBuf<double> d_coef;
+  HIP_OK(d_idx.alloc((size_t)n));
+  HIP_OK(d_coef.alloc((size_t)n));
   HIP_OK(hipMemcpy(d_idx, idx.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(d_coef, minus_one.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   if (laplace_pred_quad(h, n, 1, d_idx, d_coef, cg_max_num_it, tol, false, var_host, cg_iterations)) return -1;
@@ -2676,17 +2695,15 @@ int gpb_hip_vecchia_laplace_grad_F_current(gpb_hip_vecchia_t* h, double* gradF_h
   if (!s || !s->grad_state || !s->gvec_state) return fail("the gradient wrt the fixed effects needs the state of gpb_hip_vecchia_laplace_grad_current");
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n;
-  double* V = s->d_vec;
+  const LapWork w = lap_work(h, s, s->g_t);
   if (!s->re_ptr.empty()) {
     // repeated locations: per DATUM, in the order labels / fixed effects were handed over (grouped by random effect, Vecchia order of the random
     // effects) -- the data-scale form of likelihoods.h:6944-6966
     const int nd = s->n_data;
     if (!s->d_dptr) return fail("the data map has not been uploaded (no evaluation since gpb_hip_vecchia_laplace_set_data_map)");
-    double* d_out = nullptr;
-    HIP_OK(hipMalloc(&d_out, sizeof(double) * (size_t)nd));
-    struct Free { double* p; ~Free() { if (p) (void)hipFree(p); } } guard{ d_out };
-    const double *dW3 = s->d_gvec + (size_t)n, *dld = s->d_gvec + (size_t)2 * n, *sv = s->d_gvec + (size_t)3 * n;
-    HIP_OK(gpb::lap_grad_F_map(s->link, V, s->resp(), s->has_fe ? s->d_fe : nullptr, dld, dW3, sv, n, s->d_dptr, d_out, h->stream));
+    DevBuf<double> d_out;
+    HIP_OK(d_out.alloc((size_t)nd));
+    HIP_OK(gpb::lap_grad_F_map(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.dW3, w.sv, n, s->d_dptr, d_out, h->stream));
     std::vector<double> tmp(nd);
     HIP_OK(hipMemcpyAsync(tmp.data(), d_out, sizeof(double) * (size_t)nd, hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -2700,11 +2717,9 @@ int gpb_hip_vecchia_laplace_grad_F_current(gpb_hip_vecchia_t* h, double* gradF_h
     }
     return 0;
   }
-  double* t2 = V + (size_t)14 * n;                 // free between evaluations
-  const double *dld = s->d_gvec + (size_t)2 * n, *sv = s->d_gvec + (size_t)3 * n;
-  HIP_OK(gpb::lap_grad_F(s->link, V, s->resp(), s->has_fe ? s->d_fe : nullptr, dld, sv, n, t2, h->stream));
+  HIP_OK(gpb::lap_grad_F(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.sv, n, w.t2, h->stream));      // (t2: free between evaluations)
   std::vector<double> tmp(n);
-  HIP_OK(hipMemcpyAsync(tmp.data(), t2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(tmp.data(), w.t2, w.vb, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   for (int i = 0; i < n; ++i) gradF_host[i] = tmp[s->sigma[i]];
   API_END();
@@ -2722,8 +2737,8 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n;
   const int nd = s->re_ptr.empty() ? n : s->n_data;
-  const double *dW3 = s->d_gvec + (size_t)n, *dld = s->d_gvec + (size_t)2 * n, *sv = s->d_gvec + (size_t)3 * n;
-  HIP_OK(gpb::lap_aux_grad(s->link, s->d_vec, s->resp(), s->has_fe ? s->d_fe : nullptr, dld, dW3, sv, n, s->d_dptr, s->d_o, h->stream));
+  const LapWork w = lap_work(h, s, s->g_t);
+  HIP_OK(gpb::lap_aux_grad(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.dW3, w.sv, n, s->d_dptr, s->d_o, h->stream));
   double o3[3];
   HIP_OK(hipMemcpyAsync(o3, s->d_o, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2747,12 +2762,11 @@ int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_
       case gpb::kGaussianLatent: g_scale = -0.5 / r * o3[0] + 0.5 * nd; break;
       default: return fail("gpb_hip_vecchia_laplace_grad_aux_current: the Fisher-Laplace gradient of likelihood id %d is missing", s->link);
     }
-    const int NCB = 4, t = s->g_t, tch = (t + NCB - 1) / NCB, tc = tch * NCB;
-    const size_t nb = (size_t)n * tc;
+    const int NCB = w.NCB, t = s->g_t, tch = w.tch, tc = w.tc;
+    const size_t nb = w.nb;
     hipStream_t st = h->stream;
-    double* V = s->d_vec;
-    const double *W = V + (size_t)n, *rdw = V + (size_t)15 * n;
-    double *R = s->d_blk, *T = R + 4 * nb, *Z = R + nb;              // free after the log-determinant / the covariance-parameter gradient
+    const double *W = w.W, *rdw = w.rdw;
+    double *R = w.R, *T = w.T, *Z = w.Z;              // free after the log-determinant / the covariance-parameter gradient
     const double *U = s->d_gblk, *PIZ = s->d_gblk + nb;
     const gpb::LapLevels lv = make_levels(h, s);
     // W_r = (sum of weights) FI  ->  the per-row weight sums are W / FI: dW / d log aux = W .* (dFI / FI)
@@ -2862,17 +2876,9 @@ int gpb_hip_vecchia_fisher_std_errors(gpb_hip_vecchia_t* h, int cov_type, double
   s->grad_state = false; s->gvec_state = false;
   const int n = h->n, m = h->m;
   hipStream_t st = h->stream;
-  if (!h->d_A) {
-    HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)n * m));
-    HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)n));
-    HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)n));
-  }
+  if (lap_alloc_factor(h)) return -1;
   {
-    const bool had_y = h->has_y;
-    h->has_y = true;                       // u = B y is not used here
-    const int rc = vecchia_launch(h, gpb::MODE_FACTOR, cov_type, ratio, a, 1, nullptr, 0);
-    h->has_y = had_y;
-    if (rc) return -1;
+    if (lap_launch_factor(h, cov_type, ratio, a, 1)) return -1;
     HIP_OK(hipStreamSynchronize(st));
     h->has_factor = false; h->u_stale = false; h->has_yaux = false;   // the factor on the device no longer belongs to a y_aux computed earlier
   }
@@ -2880,12 +2886,13 @@ int gpb_hip_vecchia_fisher_std_errors(gpb_hip_vecchia_t* h, int cov_type, double
   if (!h->has_levels && build_levels(h, s)) return -1;
   if (!s->d_Ds) HIP_OK(hipMalloc(&s->d_Ds, sizeof(double) * (size_t)n));
   HIP_OK(gpb::lap_scatter(h->d_D, s->d_sigma, n, s->d_Ds, st));
-  const int t = num_rand_vec, NCB = 4, tch = (t + NCB - 1) / NCB, tc = tch * NCB;
-  const size_t blk = (size_t)n * tc;
+  const int t = num_rand_vec;
+  const LapWork w = lap_work(h, s, t);                  // (the chunk geometry; this computation has its own workspace)
+  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
+  const size_t blk = w.nb;
   // workspace of this computation only (freed at the end): probes + 8 blocks + two derivative sets
-  double* d_ws = nullptr;
-  HIP_OK(hipMalloc(&d_ws, sizeof(double) * (blk * 9 + (size_t)n * 2)));
-  struct Guard { double* p; ~Guard() { if (p) (void)hipFree(p); } } guard{d_ws};
+  DevBuf<double> d_ws;
+  HIP_OK(d_ws.alloc(blk * 9 + (size_t)n * 2));
   HIP_OK(hipMemsetAsync(d_ws, 0, sizeof(double) * (blk * 9 + (size_t)n * 2), st));
   double *Z = d_ws, *T = d_ws + blk, *U = d_ws + 2 * blk, *V0 = d_ws + 3 * blk, *V1 = d_ws + 4 * blk, *V2 = d_ws + 5 * blk, *P = d_ws + 6 * blk,
          *H = d_ws + 7 * blk, *Q = d_ws + 8 * blk, *dDs = d_ws + 9 * blk, *tmpn = d_ws + 9 * blk + n;
@@ -2940,9 +2947,8 @@ int gpb_hip_vecchia_fisher_std_errors(gpb_hip_vecchia_t* h, int cov_type, double
     HIP_OK(gpb::lap_mul(bwd_g, n, T, P, tch, NCB, st));                             // P = dA_k' T
     HIP_OK(gpb::lap_lincomb(Vk, Q, P, 1.0, 1.0, (int)blk, st));                     // V_k = Q + P
   }
-  double* d_dots = nullptr;
-  HIP_OK(hipMalloc(&d_dots, sizeof(double) * (size_t)6 * tc));
-  struct Guard2 { double* p; ~Guard2() { if (p) (void)hipFree(p); } } guard2{d_dots};
+  DevBuf<double> d_dots;
+  HIP_OK(d_dots.alloc((size_t)6 * tc));
   HIP_OK(gpb::lap_coldots(V0, V1, V0, n, tch, NCB, d_dots, st));                    // 00, 10
   HIP_OK(gpb::lap_coldots(V1, V2, V1, n, tch, NCB, d_dots + 2 * tc, st));           // 11, 21
   HIP_OK(gpb::lap_coldots(V0, V2, V2, n, tch, NCB, d_dots + 4 * tc, st));           // 02, 22
@@ -2970,28 +2976,19 @@ int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int cov_type, doub
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n, m = h->m;
   if (h->i_begin != 0 || h->i_end != n) return fail("the Vecchia-Laplace path needs the whole factor on one device");
-  if (!h->d_A) {
-    HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)n * m));
-    HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)n));
-    HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)n));
-  }
-  const bool had_y = h->has_y;
-  h->has_y = true;
-  const int rc = vecchia_launch(h, gpb::MODE_FACTOR, cov_type, var, a, 0, nullptr, 0);
-  h->has_y = had_y;
-  if (rc) return -1;
+  if (lap_alloc_factor(h)) return -1;
+  if (lap_launch_factor(h, cov_type, var, a, 0)) return -1;
   h->has_factor = true;
   if (h->lap) h->lap->grad_state = false;
-  double *dA = nullptr, *dD = nullptr;
-  HIP_OK(hipMalloc(&dA, sizeof(double) * (size_t)n * m));
-  HIP_OK(hipMalloc(&dD, sizeof(double) * (size_t)n));
+  DevBuf<double> dA, dD;
+  HIP_OK(dA.alloc((size_t)n * m));
+  HIP_OK(dD.alloc((size_t)n));
   if (m > 126) return fail("gpb_hip_vecchia_laplace_range_deriv: at most 126 neighbours (this model has %d)", m);
   if (h->d > 3) return fail("gpb_hip_vecchia_laplace_range_deriv: coordinate dimensions 1..3 (this model has %d)", h->d);
   hipError_t e = gpb::lap_range_deriv(h->d_pts, h->d_nn, h->d_A, n, m, cov_type, h->d == 3 ? 1 : 0, var, a, dA, dD, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dA_host, dA, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dD_host, dD, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(dA); (void)hipFree(dD);
   if (e != hipSuccess) return fail("HIP error: %s", hipGetErrorString(e));
   API_END();
 }
