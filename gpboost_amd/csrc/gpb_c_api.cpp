@@ -533,6 +533,13 @@ int prediction_response(REModelHip* mdl, const double* y_data, const double* fe)
 
 double range_const(const REModelHip* mdl) { return mdl->cov_type == 0 ? 1. : (mdl->cov_type == 1 ? std::sqrt(3.) : std::sqrt(5.)); }
 
+// Matern covariance with shape 0.5 / 1.5 / 2.5 (cov_type 0 / 1 / 2) on the host at the scaled distance r = a |x - x'|: e = scale exp(-r) times the shape's
+// polynomial.  A caller that multiplies its variance in afterwards passes scale = 1, so every site rounds as it always did.
+double matern_host(int cov_type, double scale, double r) {
+  const double e = scale * std::exp(-r);
+  return cov_type == 0 ? e : (cov_type == 1 ? e * (1. + r) : e * (1. + r + r * r / 3.));
+}
+
 // REModelTemplate::FindInitCovPar (re_model_template.h:4849-4968) -> RECompGP::FindInitCovPar (re_comp.h:1249-1267) ->
 // CovFunction::FindInitCovPar (cov_fcts.h:1422-1683) for one Gaussian Matern GP.  The result is used as cov_pars_ directly, i.e. it
 // is on the TRANSFORMED scale: (var(y) / 2, 1, a) with a such that the correlation is ~0.05 at half the median distance.
@@ -740,7 +747,7 @@ int vif_terms_core(int k, int d, const double* ip_colmajor, int cov_type, double
       double s2 = 0.;
       for (int c = 0; c < d; ++c) { const double t = ip_colmajor[(size_t)c * k + i] - ip_colmajor[(size_t)c * k + j]; s2 += t * t; }
       const double r = a * std::sqrt(s2), e = ratio * std::exp(-r);
-      const double kv = cov_type == 0 ? e : (cov_type == 1 ? e * (1. + r) : e * (1. + r + r * r / 3.));
+      const double kv = matern_host(cov_type, ratio, r);
       Sm0[(size_t)i * k + j] = Sm0[(size_t)j * k + i] = kv;
       if (with_grad) {      // d/d log a (GradientRangeMaternShape0_5 / 1_5 / 2_5 with transf_scale, cov_fcts.h:2535-2554)
         const double dk = cov_type == 0 ? -r * e : (cov_type == 1 ? -r * r * e : -r * r * (1. + r) * e / 3.);
@@ -2043,55 +2050,6 @@ int GPB_HIP_OptimizeGaussianWithCallback(int32_t num_data, const double* init_th
   C_API_END();
 }
 
-/* Host half of the Vecchia prediction 'order_obs_first_cond_all' (CalcPredVecchiaObservedFirstOrder with CondObsOnly = false,
-   src/GPBoost/Vecchia_utils.cpp:2061-2090), and test seam for it: given the factor rows of the APPENDED prediction points -- neighbour
-   indices into (observed, prediction) points, nn < n_obs + i for row i, -1 padded; A_i = C_nn^-1 c; D_i with the nugget, transformed scale
-   (what vecchia_point_kernel<MODE_FACTOR> leaves for them, neighbours searched with end_search_at = -1) --
-     mean = Bp^-1 (-Bpo y)          forward substitution: Bp = I - A_pp is unit lower triangular (:2061-2064)
-     cov  = sigma2 Bp^-1 Dp Bp^-T   rows of Bp^-1 by the same recursion (:2077-2090); nugget removed from the diagonal unless predict_response
-   var_out (n_pred) and cov_out (n_pred x n_pred, row-major) may each be NULL.  Dense in the number of prediction points (the reference keeps
-   Bp^-1 sparse): refused above 20000 points.  The device wiring into GPB_PredictREModel is not done yet. */
-int GPB_HIP_PredictCondAllHost(int32_t n_obs, int32_t n_pred, int32_t m, const int32_t* nn_pred, const double* A_pred, const double* D_pred,
-                               const double* y_obs, double sigma2, bool predict_response, double* mean_out, double* var_out, double* cov_out) {
-  C_API_BEGIN();
-  if (!nn_pred || !A_pred || !D_pred || !y_obs || !mean_out || n_obs < 1 || n_pred < 1 || m < 1)
-    return set_error("GPB_HIP_PredictCondAllHost: invalid argument");
-  const bool need_rows = var_out || cov_out;
-  if (need_rows && n_pred > 20000) return set_error("GPB_HIP_PredictCondAllHost: predictive (co)variances for %d points (dense limit: 20000)", n_pred);
-  std::vector<double> L;                       // row i of Bp^-1, columns 0..i (lower triangular, row-major full storage)
-  if (need_rows) L.assign((size_t)n_pred * n_pred, 0.);
-  for (int i = 0; i < n_pred; ++i) {
-    double mu = 0.;
-    if (need_rows) L[(size_t)i * n_pred + i] = 1.;
-    for (int j = 0; j < m; ++j) {
-      const int c = nn_pred[(size_t)i * m + j];
-      if (c < 0) continue;
-      if (c >= n_obs + i) return set_error("GPB_HIP_PredictCondAllHost: row %d has neighbour %d that does not precede it", i, c);
-      const double a = A_pred[(size_t)i * m + j];
-      if (c < n_obs) mu += a * y_obs[c];
-      else {
-        const int q = c - n_obs;
-        mu += a * mean_out[q];
-        if (need_rows) for (int k = 0; k <= q; ++k) L[(size_t)i * n_pred + k] += a * L[(size_t)q * n_pred + k];
-      }
-    }
-    mean_out[i] = mu;
-  }
-  if (need_rows) {
-    for (int i = 0; i < n_pred; ++i) {
-      for (int k = cov_out ? 0 : i; k <= i; ++k) {
-        double sacc = 0.;
-        for (int j = 0; j <= k; ++j) sacc += L[(size_t)i * n_pred + j] * D_pred[j] * L[(size_t)k * n_pred + j];
-        double v = sigma2 * sacc;
-        if (i == k && !predict_response) v -= sigma2;
-        if (cov_out) { cov_out[(size_t)i * n_pred + k] = v; cov_out[(size_t)k * n_pred + i] = v; }
-        if (var_out && i == k) var_out[i] = v;
-      }
-    }
-  }
-  C_API_END();
-}
-
 /* Test seam for the host half of the unique-location mapping (no device needed): uniques_out (n, the first *num_unique entries are the positions of
    the first appearances, ascending) and unique_idx_out (n) of DetermineUniqueDuplicateCoordsFast (src/GPBoost/GP_utils.cpp:472-548) as
    GPB_CreateREModel applies it to the (shuffled) coordinates of one non-Gaussian GP.  coords: column-major n x d. */
@@ -2126,578 +2084,12 @@ int GPB_HIP_GaussHermiteHost(int32_t order, double* nodes_out, double* adaptive_
   C_API_END();
 }
 
-/* c_api.h:1588-1610 -- only what the obs-only Vecchia prediction needs is kept: coordinates, prediction type, #neighbours */
-int GPB_SetPredictionData(REModelHandle handle, int32_t num_data_pred, const int32_t* cluster_ids_data_pred, const char* re_group_data_pred,
-                          const double* re_group_rand_coef_data_pred, double* gp_coords_data_pred, const double* gp_rand_coef_data_pred,
-                          const double* covariate_data_pred, const char* vecchia_pred_type, int num_neighbors_pred,
-                          double /*cg_delta_conv_pred*/, int /*nsim_var_pred*/, int /*rank_pred_approx_matrix_lanczos*/) {
-  C_API_BEGIN();
-  auto* mdl = reinterpret_cast<REModelHip*>(handle);
-  if (!mdl) return set_error("GPB_SetPredictionData: null handle");
-  const char* scope = "is not on the MI355X path of this library";
-  if (cluster_ids_data_pred || re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred || covariate_data_pred)
-    return set_error("GPB_SetPredictionData: cluster ids / grouped effects / random coefficients / covariates for prediction %s", scope);
-  if (vecchia_pred_type && vecchia_pred_type[0]) {
-    const std::string t = vecchia_pred_type;
-    // SUPPORTED_VECCHIA_PRED_TYPES_GAUSS_ of the reference; only the first is implemented on the device
-    if (t != "order_obs_first_cond_obs_only" && t != "order_obs_first_cond_all" && t != "order_pred_first" &&
-        t != "latent_order_obs_first_cond_obs_only" && t != "latent_order_obs_first_cond_all")
-      return set_error("Prediction type '%s' is not supported for the Veccia approximation ", t.c_str());
-    mdl->vecchia_pred_type = t;
-  }
-  if (num_neighbors_pred > 0) mdl->num_neighbors_pred = num_neighbors_pred;
-  if (gp_coords_data_pred) {
-    if (num_data_pred <= 0) return set_error("GPB_SetPredictionData: num_data_pred = %d", num_data_pred);
-    mdl->coords_pred.assign(gp_coords_data_pred, gp_coords_data_pred + (size_t)num_data_pred * mdl->d);
-    mdl->num_data_pred = num_data_pred;
-  }
-  C_API_END();
-}
+}  // extern "C"
 
-/* c_api.h:1640-1660 -- predictive mean and variances (or the, here diagonal, covariance matrix) at new locations for the Gaussian
- * one-cluster Vecchia model, vecchia_pred_type "order_obs_first_cond_obs_only" (REModel::Predict, re_model.cpp:1083-1215 ->
- * CalcPredVecchiaObservedFirstOrder(CondObsOnly = true), Vecchia_utils.cpp:1701-2060) */
-int GPB_PredictREModel(REModelHandle handle, const double* y_data, int32_t num_data_pred, double* out_predict, bool predict_cov_mat,
-                       bool predict_var, bool predict_response, bool sample_posterior, bool sample_prior, int /*num_post_samples*/,
-                       int /*num_prior_samples*/, const int32_t* cluster_ids_data_pred, const char* re_group_data_pred,
-                       const double* re_group_rand_coef_data_pred, double* gp_coords_data_pred, const double* gp_rand_coef_data_pred,
-                       const double* cov_pars, const double* covariate_data_pred, bool use_saved_data, const double* fixed_effects,
-                       const double* fixed_effects_pred) {
-  C_API_BEGIN();
-  auto* mdl = reinterpret_cast<REModelHip*>(handle);
-  if (!mdl || !out_predict) return set_error("GPB_PredictREModel: null argument");
-  if (mdl && mdl->vif && mdl->likelihood == "gaussian") {
-    // full-scale Vecchia, 'order_obs_first_cond_obs_only' (the reference's default for Gaussian data; CalcPredVecchiaObservedFirstOrder with the
-    // full_scale_vecchia arguments, Vecchia_utils.cpp:1701-2060; re_model_template.h:4041-4056): y_p = C_p Sigma_m^-1 eta + e_p with the residual
-    // e_p conditioning on the nearest observed points -> mean = A_p y_nn + (B C)_p W^-1 (B C)' D^-1 B y, var = sigma2 (D_p + (B C)_p W^-1 (B C)_p')
-    const char* vscope = "is not on the MI355X path of this library (full-scale Vecchia prediction: 'order_obs_first_cond_obs_only' / 'order_obs_first_cond_all', no covariates / samples)";
-    if (sample_posterior || sample_prior) return set_error("GPB_PredictREModel: samples of a full-scale Vecchia model %s", vscope);
-    if (predict_cov_mat && predict_var) return set_error("Calculation of both the predictive covariance matrix and variances is not supported. Choose one option (predict_cov_mat or predict_var)");
-    if (cluster_ids_data_pred || re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred || covariate_data_pred || mdl->p_cov > 0)
-      return set_error("GPB_PredictREModel: cluster ids / grouped effects / random coefficients / covariates for prediction %s", vscope);
-    // (the reference has exactly these two for full-scale Vecchia models: 'order_pred_first' and the latent types are fatal there, re_model_template.h:4072-4110)
-    const bool v_cond_all = mdl->vecchia_pred_type == "order_obs_first_cond_all";
-    if (mdl->vecchia_pred_type != "order_obs_first_cond_obs_only" && !v_cond_all) return set_error("GPB_PredictREModel: vecchia_pred_type '%s' of a full-scale Vecchia model %s", mdl->vecchia_pred_type.c_str(), vscope);
-    const double* cpv = gp_coords_data_pred;
-    int npv = num_data_pred;
-    if (use_saved_data) { cpv = mdl->coords_pred.empty() ? nullptr : mdl->coords_pred.data(); npv = mdl->num_data_pred; }
-    if (!cpv || npv <= 0) return set_error("GPB_PredictREModel: no coordinates for prediction (gp_coords_data_pred / GPB_SetPredictionData)");
-    double trv[3];
-    if (cov_pars) { double c3[3] = {cov_pars[0], cov_pars[1], cov_pars[2]}; if (transform_cov_pars(mdl, c3, trv)) return -1; }
-    else {
-      if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");
-      std::copy(mdl->cov_pars_tr, mdl->cov_pars_tr + 3, trv);
-    }
-    if (!y_data && !mdl->y_set) return set_error("GPB_PredictREModel: y_data is NULL and no response has been set by an earlier call");
-    const double* fev = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-    if (prediction_response(mdl, y_data, fev)) return -1;
-    VifSolve vs;
-    double t3[3];
-    if (vif_terms(mdl, trv[1], trv[2], t3, &vs)) return -1;
-    int nnpv = mdl->num_neighbors_pred > 0 ? mdl->num_neighbors_pred : 2 * mdl->num_neighbors;
-    if (nnpv > (v_cond_all ? mdl->n + npv - 1 : mdl->n)) nnpv = v_cond_all ? mdl->n + npv - 1 : mdl->n;
-    if (nnpv > 126) nnpv = 126;
-    const int kv = mdl->num_ind_points;
-    std::vector<double> up(npv), Dp(npv), BC((size_t)npv * kv);
-    if (v_cond_all) {
-      // 'order_obs_first_cond_all' (CalcPredVecchiaObservedFirstOrder, CondObsOnly = false, Vecchia_utils.cpp:1975-2046): the device returns the rows of
-      // [Bpo Bp] of the appended points, -(Bpo y) and (B~ C~)_p; here the forward substitutions with Bp = I - A_pp (unit lower triangular: a neighbour
-      // precedes its point) --  mean = Bp^-1 (-Bpo y + (B~ C~)_p v),  T = Bp^-1 (B~ C~)_p,  rows of Bp^-1 --  and
-      // cov = sigma2 (Bp^-1 Dp Bp^-T + T W^-1 T')  [- sigma2 I for the latent process].  The reference's eight-term expression (:2028-2046) is T W^-1 T'
-      // written out with W = Sigma_m + (B C)' D^-1 (B C).  Dense in the number of prediction points, as the 'cond_all' type of the plain Vecchia model here.
-      const bool second2 = predict_var || predict_cov_mat;
-      if (second2 && npv > 20000) return set_error("GPB_PredictREModel: predictive (co)variances of 'order_obs_first_cond_all' for %d points (dense limit: 20000)", npv);
-      int mu_ = 0;
-      std::vector<int32_t> nnr((size_t)npv * nnpv);
-      std::vector<double> Ap((size_t)npv * nnpv);
-      if (gpb_hip_vecchia_vif_predict_cond_all(mdl->vh, npv, cpv, nnpv, mdl->ip.data(), mdl->cov_type, trv[1], trv[2], vs.Linv.data(), &mu_, nnr.data(), Ap.data(),
-                                               up.data(), Dp.data(), BC.data(), nullptr)) return shim_error();
-      std::vector<double> Lr(second2 ? (size_t)npv * npv : 0, 0.);       // rows of Bp^-1
-      std::vector<double> mean(npv);
-      for (int i = 0; i < npv; ++i) {
-        double* bc = BC.data() + (size_t)i * kv;
-        if (second2) Lr[(size_t)i * npv + i] = 1.;
-        double w = -up[i];
-        for (int j = 0; j < kv; ++j) w += bc[j] * vs.v[j];
-        for (int j = 0; j < mu_; ++j) {
-          const int c = nnr[(size_t)i * mu_ + j];
-          if (c < mdl->n) continue;                              // (-1 padding and observed neighbours: already in u and BC)
-          const int q = c - mdl->n;
-          if (q >= i) return set_error("GPB_PredictREModel: prediction point %d has neighbour %d that does not precede it", i, q);
-          const double aij = Ap[(size_t)i * mu_ + j];
-          w += aij * mean[q];
-          if (second2) {
-            const double* bq = BC.data() + (size_t)q * kv;       // (already T_q: rows are finished in order)
-            for (int r = 0; r < kv; ++r) bc[r] += aij * bq[r];
-            for (int r = 0; r <= q; ++r) Lr[(size_t)i * npv + r] += aij * Lr[(size_t)q * npv + r];
-          }
-        }
-        mean[i] = w;
-        out_predict[i] = w + (fixed_effects_pred ? fixed_effects_pred[i] : 0.);
-      }
-      if (second2) {
-        std::vector<double> T((size_t)npv * kv);
-        for (int i = 0; i < npv; ++i) {                          // T_i <- L_W^-1 T_i
-          const double* bc = BC.data() + (size_t)i * kv;
-          double* tmp = T.data() + (size_t)i * kv;
-          for (int r = 0; r < kv; ++r) {
-            double v = bc[r];
-            for (int j = 0; j < r; ++j) v -= vs.Lw[(size_t)r * kv + j] * tmp[j];
-            tmp[r] = v / vs.Lw[(size_t)r * kv + r];
-          }
-        }
-        for (int i = 0; i < npv; ++i) {
-          for (int j = predict_cov_mat ? 0 : i; j <= i; ++j) {
-            double qq = 0.;
-            for (int r = 0; r < kv; ++r) qq += T[(size_t)i * kv + r] * T[(size_t)j * kv + r];
-            for (int r = 0; r <= j; ++r) qq += Lr[(size_t)i * npv + r] * Dp[r] * Lr[(size_t)j * npv + r];
-            const double v = trv[0] * (qq - ((i == j && !predict_response) ? 1. : 0.));
-            if (predict_cov_mat) { out_predict[npv + (size_t)i * npv + j] = v; out_predict[npv + (size_t)j * npv + i] = v; }
-            else out_predict[npv + i] = v;
-          }
-        }
-      }
-      mdl->yaux_valid = false;
-      return 0;
-    }
-    if (gpb_hip_vecchia_vif_predict_obs_only(mdl->vh, npv, cpv, nnpv, mdl->ip.data(), mdl->cov_type, trv[1], trv[2], vs.Linv.data(), up.data(), Dp.data(), BC.data(), nullptr))
-      return shim_error();
-    // T = L_W^-1 (B C)_p' column by column (only when second moments are asked for): var_p = D_p + ||T_p||^2, and -- the residuals of two
-    // prediction points being independent given the observed ones (Bp = I) -- cov_pq = T_p . T_q off the diagonal
-    const bool second = predict_var || predict_cov_mat;
-    std::vector<double> T(second ? (size_t)npv * kv : 0);
-    for (int i = 0; i < npv; ++i) {
-      const double* bc = BC.data() + (size_t)i * kv;
-      double mu = -up[i];
-      for (int j = 0; j < kv; ++j) mu += bc[j] * vs.v[j];
-      out_predict[i] = mu + (fixed_effects_pred ? fixed_effects_pred[i] : 0.);
-      if (second) {
-        double* tmp = T.data() + (size_t)i * kv;
-        for (int r = 0; r < kv; ++r) {
-          double v = bc[r];
-          for (int j = 0; j < r; ++j) v -= vs.Lw[(size_t)r * kv + j] * tmp[j];
-          tmp[r] = v / vs.Lw[(size_t)r * kv + r];
-        }
-      }
-    }
-    if (second) for (int i = 0; i < npv; ++i) {
-      for (int j = predict_cov_mat ? 0 : i; j <= i; ++j) {
-        double qq = 0.;
-        for (int r = 0; r < kv; ++r) qq += T[(size_t)i * kv + r] * T[(size_t)j * kv + r];
-        const double v = trv[0] * (qq + (i == j ? Dp[i] - (predict_response ? 0. : 1.) : 0.));
-        if (predict_cov_mat) { out_predict[npv + (size_t)i * npv + j] = v; out_predict[npv + (size_t)j * npv + i] = v; }
-        else out_predict[npv + i] = v;
-      }
-    }
-    mdl->yaux_valid = false;
-    return 0;
-  }
-  const char* scope = "is not on the MI355X path of this library (prediction: one-cluster Gaussian Vecchia model, 'order_obs_first_cond_obs_only')";
-  if (mdl->likelihood != "gaussian" && !mdl->eh && mdl->vhs.size() == 1) {
-    // non-Gaussian (Vecchia-Laplace) models, the reference's default prediction type for them ('latent_order_obs_first_cond_obs_only'):
-    //   latent mean -Bpo mode, latent (co)variances Dp + Bpo (Sigma^-1 + W)^-1 Bpo' (PredictLaplaceApproxVecchia, likelihoods.h:8563-8824 -- the
-    //   exact value of its "cholesky" branch, which its "iterative" branch estimates with nsim_var_pred random vectors), and the response-scale
-    //   predictions from them (PredictResponse, :9626-9672).  Repeated prediction locations share a random effect (re_model_template.h:3976-3988).
-    const char* lscope = "is not on the MI355X path of this library (non-Gaussian likelihoods: 'latent_order_obs_first_cond_obs_only' / 'latent_order_obs_first_cond_all', no samples)";
-    if (sample_posterior || sample_prior) return set_error("GPB_PredictREModel: posterior / prior samples %s", lscope);
-    if (predict_response && predict_cov_mat) return set_error("Calculation of the predictive covariance matrix is not supported when predicting the response variable (label) for non-Gaussian likelihoods");   // :3526-3529
-    if (predict_cov_mat && predict_var) return set_error("Calculation of both the predictive covariance matrix and variances is not supported. Choose one option (predict_cov_mat or predict_var)");
-    if (cluster_ids_data_pred || re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred)
-      return set_error("GPB_PredictREModel: cluster ids / grouped effects / random coefficients for prediction %s", lscope);
-    if (mdl->p_cov > 0 && !mdl->coef_estimated) return set_error("GPB_PredictREModel: the model has covariates but no estimated coefficients");
-    if (mdl->p_cov > 0 && !covariate_data_pred) return set_error("No covariate data is provided in 'covariate_data_pred' but the model has linear regression covariates");   // re_model.cpp Predict
-    if (mdl->p_cov == 0 && covariate_data_pred) return set_error("Covariate data is provided in 'covariate_data_pred' but the model has no linear regression covariates");
-    if (mdl->p_cov > 0 && use_saved_data) return set_error("GPB_PredictREModel: saved prediction data together with covariates %s", lscope);
-    const std::string& pt = mdl->vecchia_pred_type;
-    // for non-Gaussian likelihoods the two 'order_obs_first_*' names mean their latent counterparts (re_model_template.h:7112-7124)
-    const bool lat_cond_all = pt == "latent_order_obs_first_cond_all" || pt == "order_obs_first_cond_all";
-    if (!pt.empty() && pt != "order_obs_first_cond_obs_only" && pt != "latent_order_obs_first_cond_obs_only" && !lat_cond_all)
-      return set_error("GPB_PredictREModel: vecchia_pred_type '%s' %s", pt.c_str(), lscope);
-    // full-scale Vecchia (round 6; PredictLaplaceApproxFSVA, likelihoods.h:7999-8535): means, variances and covariance matrices of both latent prediction types;
-    // with covariates the mode is found at the location parameter fixed effects + X beta and X_pred beta joins the latent mean, as for the Vecchia models
-    const double* cpl = gp_coords_data_pred;
-    int npl = num_data_pred;
-    if (use_saved_data) { cpl = mdl->coords_pred.empty() ? nullptr : mdl->coords_pred.data(); npl = mdl->num_data_pred; }
-    if (!cpl || npl <= 0) return set_error("GPB_PredictREModel: no coordinates for prediction (gp_coords_data_pred / GPB_SetPredictionData)");
-    if (!y_data && !mdl->y_set) return set_error("GPB_PredictREModel: y_data is NULL and no response has been set by an earlier call");
-    if (predict_cov_mat && npl > 20000) return set_error("GPB_PredictREModel: predictive covariance matrix for %d points (dense limit: 20000)", npl);
-    double s12, rho;
-    if (cov_pars) { s12 = cov_pars[0]; rho = cov_pars[1]; }
-    else {
-      if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");
-      s12 = mdl->cov_pars_tr[0]; rho = range_const(mdl) / mdl->cov_pars_tr[1];
-    }
-    if (!(s12 > 0.) || !(rho > 0.)) return set_error("Covariance parameters need to be positive (found %g, %g)", s12, rho);
-    const double* fel = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-    std::vector<double> fe_lin;                  // location parameter of the observed data = fixed effects + X beta (UpdateFixedEffects, re_model_template.h:2859-2871)
-    if (mdl->p_cov > 0) {
-      fe_lin.assign(mdl->n, 0.);
-      for (int i = 0; i < mdl->n; ++i) { double v = fel ? fel[i] : 0.; for (int j = 0; j < mdl->p_cov; ++j) v += mdl->X[(size_t)j * mdl->n + i] * mdl->beta[j]; fe_lin[i] = v; }
-      fel = fe_lin.data();
-    }
-    if (y_data) { if (laplace_upload_data(mdl, y_data, fel)) return -1; }
-    else if (laplace_upload_fixed_effects(mdl, fel)) return -1;
-    const double a_tr = range_const(mdl) / rho;
-    std::vector<double> mode(mdl->n_re > 0 ? mdl->n_re : mdl->n);
-    if (laplace_prepare_preconditioner(mdl)) return -1;
-    if (gpb_hip_vecchia_laplace_logit(mdl->vh, mdl->cov_type, s12, a_tr, mdl->num_rand_vec_trace, mdl->seed_rand_vec_trace, mdl->cg_max_num_it,
-                                      mdl->cg_max_num_it_tridiag, mdl->cg_delta_conv, mdl->delta_conv_mode_finding, 1, mdl->lap_info, mode.data()))
-      return shim_error();
-    if (!mdl->vif && gpb_hip_vecchia_set_y(mdl->vh, mode.data())) return shim_error();          // the "response" of the prediction is the mode (Vecchia order)
-    const int nnpl = mdl->num_neighbors_pred > 0 ? mdl->num_neighbors_pred : 2 * mdl->num_neighbors;     // re_model_template.h:299
-    const bool need_var = predict_var || predict_response;            // every likelihood on the path needs the latent variance for its response mean
-    // unique prediction locations: first appearances, in the order given (DetermineUniqueDuplicateCoordsFast on the prediction coordinates)
-    const int dl = mdl->d;
-    std::vector<double> cpv(cpl, cpl + (size_t)npl * dl);
-    std::vector<int> uq, ui;
-    unique_locations(cpv, npl, dl, &uq, &ui);
-    const int nu = (int)uq.size();
-    std::vector<double> cu((size_t)nu * dl);
-    for (int j = 0; j < dl; ++j) for (int u = 0; u < nu; ++u) cu[(size_t)j * nu + u] = cpv[(size_t)j * npl + uq[u]];
-    std::vector<double> mu_u(nu), var_u(need_var ? nu : 0), cov_u(predict_cov_mat ? (size_t)nu * nu : 0);
-    int cg_it = 0;
-    if (mdl->vif) {      // both latent types in one call: a negative neighbour count = 'latent_order_obs_first_cond_all'
-      const int nnv = std::min(nnpl, 126);
-      if (gpb_hip_vecchia_vif_laplace_predict(mdl->vh, nu, cu.data(), lat_cond_all ? -nnv : nnv, mdl->cov_type, s12, a_tr, mdl->cg_max_num_it, kPredVarCgTol, mu_u.data(),
-                                              need_var ? var_u.data() : nullptr, predict_cov_mat ? cov_u.data() : nullptr, nullptr, &cg_it)) return shim_error();
-    } else if (lat_cond_all) {
-      // 'latent_order_obs_first_cond_all' (PredictLaplaceApproxVecchia with CondObsOnly = false, likelihoods.h:8603-8606, 8790-8821): the prediction points
-      // condition on the observed AND the preceding prediction points.  Device: factor rows of the appended points (latent: no nugget); host: the
-      // rows of Bp^-1 (forward substitution, as GPB_HIP_PredictCondAllHost) and of C = Bp^-1 Bpo; device: the quadratic forms C (Sigma^-1 + W)^-1 C'.
-      //   mean = -C mode,   cov = Bp^-1 Dp Bp^-T + C (Sigma^-1 + W)^-1 C'
-      if (nu > 5000) return set_error("GPB_PredictREModel: '%s' for %d > 5000 distinct prediction locations %s", pt.c_str(), nu, lscope);
-      const int n_obs = mdl->n_re > 0 ? mdl->n_re : mdl->n;
-      int mcap = std::min(nnpl, 126);
-      if (mcap > n_obs + nu - 1) mcap = n_obs + nu - 1;
-      int mu_ = 0;
-      std::vector<int32_t> nnr((size_t)nu * mcap);
-      std::vector<double> Ap((size_t)nu * mcap), Dp(nu);
-      if (gpb_hip_vecchia_predict_cond_all_latent(mdl->vh, nu, cu.data(), mcap, mdl->cov_type, s12, a_tr, &mu_, nnr.data(), Ap.data(), Dp.data(), nullptr)) return shim_error();
-      std::vector<double> R((size_t)nu * nu, 0.);                       // rows of Bp^-1 (unit lower triangular)
-      std::vector<std::vector<std::pair<int, double>>> Crow(nu);        // rows of C = Bp^-1 Bpo as (column, value), columns ascending
-      std::vector<double> acc(n_obs, 0.); std::vector<char> seen(n_obs, 0); std::vector<int> touched;
-      for (int k = 0; k < nu; ++k) {
-        double* Rk = R.data() + (size_t)k * nu;
-        Rk[k] = 1.;
-        for (int j = 0; j < mu_; ++j) {
-          const int c = nnr[(size_t)k * mu_ + j];
-          if (c < n_obs) continue;
-          if (c >= n_obs + k) return set_error("GPB_PredictREModel: prediction point %d has neighbour %d that does not precede it", k, c - n_obs);
-          const double av = Ap[(size_t)k * mu_ + j];
-          const double* Rj = R.data() + (size_t)(c - n_obs) * nu;
-          for (int q = 0; q <= c - n_obs; ++q) Rk[q] += av * Rj[q];       // Bp = I - A_pp  =>  row_k(Bp^-1) = e_k + sum_j A_kj row_j(Bp^-1)
-        }
-        touched.clear();
-        for (int q = 0; q <= k; ++q) {
-          const double rq = Rk[q];
-          if (rq == 0.) continue;
-          for (int j = 0; j < mu_; ++j) {
-            const int c = nnr[(size_t)q * mu_ + j];
-            if (c < 0 || c >= n_obs) continue;
-            if (!seen[c]) { seen[c] = 1; touched.push_back(c); }            // every column once (the device writes one right-hand-side entry per column)
-            acc[c] += rq * (-Ap[(size_t)q * mu_ + j]);                     // Bpo = -A_po
-          }
-        }
-        std::sort(touched.begin(), touched.end());
-        double m_k = 0.;
-        for (int c : touched) { Crow[k].emplace_back(c, acc[c]); m_k -= acc[c] * mode[c]; acc[c] = 0.; seen[c] = 0; }
-        mu_u[k] = m_k;
-      }
-      if (need_var || predict_cov_mat) {
-        size_t mmax = 1;
-        for (int k = 0; k < nu; ++k) mmax = std::max(mmax, Crow[k].size());
-        std::vector<int32_t> cols((size_t)nu * mmax, -1);
-        std::vector<double> vals((size_t)nu * mmax, 0.);
-        for (int k = 0; k < nu; ++k) for (size_t e = 0; e < Crow[k].size(); ++e) { cols[(size_t)k * mmax + e] = Crow[k][e].first; vals[(size_t)k * mmax + e] = Crow[k][e].second; }
-        std::vector<double> q(predict_cov_mat ? (size_t)nu * nu : (size_t)nu);
-        if (gpb_hip_vecchia_laplace_quad_forms(mdl->vh, nu, (int)mmax, cols.data(), vals.data(), mdl->cg_max_num_it, kPredVarCgTol, predict_cov_mat ? 1 : 0, q.data(), &cg_it)) return shim_error();
-        for (int r = 0; r < nu; ++r)
-          for (int c2 = (predict_cov_mat ? 0 : r); c2 <= r; ++c2) {      // prior part Bp^-1 Dp Bp^-T (lower triangle; the diagonal only for variances)
-            double pr = 0.;
-            for (int j = 0; j <= c2; ++j) pr += R[(size_t)r * nu + j] * Dp[j] * R[(size_t)c2 * nu + j];
-            if (predict_cov_mat) { cov_u[(size_t)r * nu + c2] = cov_u[(size_t)c2 * nu + r] = pr + q[(size_t)r * nu + c2]; }
-            if (r == c2 && need_var) var_u[r] = pr + (predict_cov_mat ? q[(size_t)r * nu + r] : q[r]);
-          }
-      }
-    } else if (gpb_hip_vecchia_laplace_predict(mdl->vh, nu, cu.data(), std::min(nnpl, 126), mdl->cov_type, s12, a_tr, mdl->cg_max_num_it, kPredVarCgTol, mu_u.data(),
-                                        need_var ? var_u.data() : nullptr, predict_cov_mat ? cov_u.data() : nullptr, nullptr, &cg_it))
-      return shim_error();
-    std::vector<double> mu(npl), var(need_var ? npl : 0);
-    for (int k = 0; k < npl; ++k) { mu[k] = mu_u[ui[k]]; if (need_var) var[k] = var_u[ui[k]]; }
-    if (fixed_effects_pred) for (int k = 0; k < npl; ++k) mu[k] += fixed_effects_pred[k];
-    if (mdl->p_cov > 0) for (int j = 0; j < mdl->p_cov; ++j) for (int k = 0; k < npl; ++k) mu[k] += covariate_data_pred[(size_t)j * npl + k] * mdl->beta[j];   // + X_pred beta (:3868-3880)
-    if (predict_response) {
-      if (!predict_response_host(mdl->likelihood, npl, mu.data(), var.data(), predict_var, mdl->delta_conv_mode_finding, mdl->aux_pars[0]))
-        return set_error("GPB_PredictREModel: response predictions for likelihood '%s' %s", mdl->likelihood.c_str(), lscope);
-    }
-    std::copy(mu.begin(), mu.end(), out_predict);
-    if (predict_var) std::copy(var.begin(), var.end(), out_predict + npl);
-    if (predict_cov_mat)            // Zpred cov Zpred' (re_model_template.h:4306-4316), column-major like the reference's output (symmetric)
-      for (int i = 0; i < npl; ++i) for (int j = 0; j < npl; ++j) out_predict[(size_t)npl + (size_t)i * npl + j] = cov_u[(size_t)ui[j] * nu + ui[i]];
-    return 0;
-  }
-  if (mdl->likelihood == "gaussian" && mdl->eh) {
-    // exact GP (gp_approx = "none"): mean = Sigma_po Psi^-1 y, covariance = Sigma_pp [+ sigma2 I] - Sigma_po Psi^-1 Sigma_op (the dense Gaussian
-    // branch of REModelTemplate::Predict, re_model_template.h:4239-4330); both reductions are blocks of one Schur complement on the device
-    const char* escope = "is not on the MI355X path of this library (exact GP prediction: coordinates only, no covariates / samples)";
-    if (sample_posterior || sample_prior) return set_error("GPB_PredictREModel: posterior / prior samples %s", escope);
-    if (predict_cov_mat && predict_var) return set_error("Calculation of both the predictive covariance matrix and variances is not supported. Choose one option (predict_cov_mat or predict_var)");
-    if (cluster_ids_data_pred || re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred || covariate_data_pred || mdl->p_cov > 0)
-      return set_error("GPB_PredictREModel: cluster ids / grouped effects / random coefficients / covariates for prediction %s", escope);
-    const double* cpe = gp_coords_data_pred;
-    int npe = num_data_pred;
-    if (use_saved_data) { cpe = mdl->coords_pred.empty() ? nullptr : mdl->coords_pred.data(); npe = mdl->num_data_pred; }
-    if (!cpe || npe <= 0) return set_error("GPB_PredictREModel: no coordinates for prediction (gp_coords_data_pred / GPB_SetPredictionData)");
-    double tre[3];
-    if (cov_pars) { double c3[3] = {cov_pars[0], cov_pars[1], cov_pars[2]}; if (transform_cov_pars(mdl, c3, tre)) return -1; }
-    else {
-      if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");
-      std::copy(mdl->cov_pars_tr, mdl->cov_pars_tr + 3, tre);
-    }
-    if (!y_data && !mdl->y_set) return set_error("GPB_PredictREModel: y_data is NULL and no response has been set by an earlier call");
-    const double* fee = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-    if (prediction_response(mdl, y_data, fee)) return -1;
-    const bool need_cov = predict_var || predict_cov_mat;
-    std::vector<double> q;
-    if (need_cov) q.resize((size_t)npe * npe);
-    if (gpb_hip_exact_predict(mdl->eh, mdl->cov_type, tre[1], tre[2], npe, cpe, out_predict, need_cov ? q.data() : nullptr)) return shim_error();
-    if (fixed_effects_pred) for (int k = 0; k < npe; ++k) out_predict[k] += fixed_effects_pred[k];
-    const double nug = predict_response ? 1. : 0.;
-    if (predict_var) for (int k = 0; k < npe; ++k) out_predict[npe + k] = tre[0] * (tre[1] + nug - q[(size_t)k * npe + k]);
-    if (predict_cov_mat) {
-      auto kern = [&](double dist) {
-        const double r = tre[2] * dist, e = tre[1] * std::exp(-r);
-        return mdl->cov_type == 0 ? e : (mdl->cov_type == 1 ? e * (1. + r) : e * (1. + r + r * r / 3.));
-      };
-      for (int i = 0; i < npe; ++i)
-        for (int j = 0; j <= i; ++j) {
-          double s2 = 0.;
-          for (int c = 0; c < mdl->d; ++c) { const double dd = cpe[(size_t)c * npe + i] - cpe[(size_t)c * npe + j]; s2 += dd * dd; }
-          const double v = tre[0] * ((i == j ? tre[1] + nug : kern(std::sqrt(s2))) - q[(size_t)i * npe + j]);
-          out_predict[npe + (size_t)i * npe + j] = v; out_predict[npe + (size_t)j * npe + i] = v;
-        }
-    }
-    mdl->yaux_valid = false;
-    return 0;
-  }
-  if (mdl->likelihood == "gaussian" && !mdl->eh && (mdl->vhs.size() > 1 || cluster_ids_data_pred)) {
-    // Several clusters = independent realisations of the GP (cluster_ids_data of GPB_CreateREModel) and / or cluster ids for the prediction points:
-    // REModelTemplate::Predict treats every prediction cluster on its own (re_model_template.h:3700-3760) -- a cluster WITH observations conditions on
-    // those observations only (Case 2, :3940-4330: here the one-cluster path below on a view of that cluster's device state); a cluster WITHOUT
-    // observations gets the prior (Case 1, :3750-3936: mean = fixed effects, covariance sigma1_2 k(.) [+ sigma2 for the response]); no covariance
-    // between clusters.
-    const char* cscope = "is not on the MI355X path of this library (prediction with cluster ids: Gaussian Vecchia model, no covariates / saved data / samples)";
-    if (sample_posterior || sample_prior) return set_error("GPB_PredictREModel: posterior / prior samples %s", cscope);
-    if (predict_cov_mat && predict_var) return set_error("Calculation of both the predictive covariance matrix and variances is not supported. Choose one option (predict_cov_mat or predict_var)");
-    if (re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred || covariate_data_pred || mdl->p_cov > 0 || use_saved_data)
-      return set_error("GPB_PredictREModel: grouped effects / random coefficients / covariates / saved prediction data %s", cscope);
-    if (!cluster_ids_data_pred) return set_error("Missing cluster_id data ('cluster_ids_pred') for making predictions");   // :3522-3524
-    const int np = num_data_pred;
-    if (!gp_coords_data_pred || np <= 0) return set_error("GPB_PredictREModel: no coordinates for prediction (gp_coords_data_pred)");
-    double c3[3], tr[3];
-    if (cov_pars) std::copy(cov_pars, cov_pars + 3, c3);
-    else {
-      if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");
-      transform_back(mdl, mdl->cov_pars_tr, c3);
-    }
-    if (transform_cov_pars(mdl, c3, tr)) return -1;
-    if (!y_data && !mdl->y_set) return set_error("GPB_PredictREModel: y_data is NULL and no response has been set by an earlier call");
-    const double* fe = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-    if (prediction_response(mdl, y_data, fe)) return -1;   // as in the one-cluster path: the residual becomes the response
-    mdl->yaux_valid = false;
-    // prediction points by cluster, clusters in the order of their first appearance
-    std::vector<int32_t> pid; std::vector<std::vector<int>> pidx;
-    for (int i = 0; i < np; ++i) {
-      size_t k = 0;
-      while (k < pid.size() && pid[k] != cluster_ids_data_pred[i]) ++k;
-      if (k == pid.size()) { pid.push_back(cluster_ids_data_pred[i]); pidx.emplace_back(); }
-      pidx[k].push_back(i);
-    }
-    const int d = mdl->d;
-    if (predict_cov_mat) std::fill(out_predict + np, out_predict + np + (size_t)np * np, 0.);
-    for (size_t pc = 0; pc < pid.size(); ++pc) {
-      const std::vector<int>& ix = pidx[pc];
-      const int npc = (int)ix.size();
-      int ci = -1;
-      if (mdl->cluster_id_values.empty()) { if (pid[pc] == 0) ci = 0; }
-      else for (size_t k = 0; k < mdl->cluster_id_values.size(); ++k) if (mdl->cluster_id_values[k] == pid[pc]) { ci = (int)k; break; }
-      std::vector<double> cc((size_t)npc * d), fep;
-      for (int j = 0; j < d; ++j) for (int k = 0; k < npc; ++k) cc[(size_t)j * npc + k] = gp_coords_data_pred[(size_t)j * np + ix[k]];
-      if (fixed_effects_pred) { fep.resize(npc); for (int k = 0; k < npc; ++k) fep[k] = fixed_effects_pred[ix[k]]; }
-      std::vector<double> outc((size_t)npc * (predict_cov_mat ? 1 + (size_t)npc : (predict_var ? 2 : 1)), 0.);
-      if (ci < 0) {
-        // no observations for this cluster: the prior.  The reference builds a Vecchia approximation of the prior among these points
-        // (:3760-3838), which is exact for up to num_neighbors + 1 of them; beyond that only the variances are on this path.
-        for (int k = 0; k < npc; ++k) outc[k] = fixed_effects_pred ? fep[k] : 0.;
-        const double vdiag = tr[0] * (tr[1] + (predict_response ? 1. : 0.));
-        if (predict_var) for (int k = 0; k < npc; ++k) outc[npc + k] = vdiag;
-        if (predict_cov_mat) {
-          if (npc > mdl->num_neighbors + 1) return set_error("GPB_PredictREModel: covariance matrix of %d prediction points in a cluster without observations (more than num_neighbors + 1 = %d) %s", npc, mdl->num_neighbors + 1, cscope);
-          for (int a1 = 0; a1 < npc; ++a1) for (int b1 = 0; b1 < npc; ++b1) {
-            double s2 = 0.;
-            for (int j = 0; j < d; ++j) { const double t = cc[(size_t)j * npc + a1] - cc[(size_t)j * npc + b1]; s2 += t * t; }
-            const double r = tr[2] * std::sqrt(s2), e = std::exp(-r);
-            const double kv = mdl->cov_type == 0 ? e : (mdl->cov_type == 1 ? e * (1. + r) : e * (1. + r + r * r / 3.));
-            outc[npc + (size_t)a1 * npc + b1] = a1 == b1 ? vdiag : tr[0] * tr[1] * kv;
-          }
-        }
-      } else {
-        // a view of cluster ci as a one-cluster model: shares the device state and the resident response, owns nothing
-        REModelHip view;
-        const auto disown = scope_exit_api([&] { view.vhs.clear(); view.vh = nullptr; view.ybuf = nullptr; view.ybuf_cap = 0; });
-        const int o0 = mdl->cl_off[ci], nc = mdl->cl_off[ci + 1] - o0;
-        view.n = nc; view.d = d; view.m = mdl->m; view.num_neighbors = mdl->num_neighbors; view.cov_type = mdl->cov_type;
-        view.perm.resize(nc); std::iota(view.perm.begin(), view.perm.end(), 0);
-        view.vh = mdl->vhs[ci]; view.vhs.assign(1, view.vh); view.cl_off = {0, nc};
-        view.has_weights = mdl->has_weights;
-        if (mdl->has_weights) view.nug_v.assign(mdl->nug_v.begin() + o0, mdl->nug_v.begin() + o0 + nc);
-        view.ybuf = mdl->ybuf + o0; view.ybuf_cap = (size_t)nc; view.y_set = true;
-        view.vecchia_pred_type = mdl->vecchia_pred_type; view.num_neighbors_pred = mdl->num_neighbors_pred;
-        if (GPB_PredictREModel(&view, nullptr, npc, outc.data(), predict_cov_mat, predict_var, predict_response, false, false, 0, 0, nullptr, nullptr, nullptr,
-                               cc.data(), nullptr, c3, nullptr, false, nullptr, fixed_effects_pred ? fep.data() : nullptr)) return -1;
-      }
-      for (int k = 0; k < npc; ++k) out_predict[ix[k]] = outc[k];
-      if (predict_var) for (int k = 0; k < npc; ++k) out_predict[np + ix[k]] = outc[npc + k];
-      if (predict_cov_mat)
-        for (int a1 = 0; a1 < npc; ++a1) for (int b1 = 0; b1 < npc; ++b1) out_predict[np + (size_t)ix[a1] * np + ix[b1]] = outc[npc + (size_t)a1 * npc + b1];
-    }
-    return 0;
-  }
-  if (mdl->likelihood != "gaussian" || mdl->eh || mdl->vhs.size() != 1) return set_error("GPB_PredictREModel: this model %s", scope);
-  if (sample_posterior || sample_prior) return set_error("GPB_PredictREModel: posterior / prior samples %s", scope);
-  if (predict_cov_mat && predict_var) return set_error("Calculation of both the predictive covariance matrix and variances is not supported. Choose one option (predict_cov_mat or predict_var)");   // re_model.cpp Predict
-  if (cluster_ids_data_pred || re_group_data_pred || re_group_rand_coef_data_pred || gp_rand_coef_data_pred)
-    return set_error("GPB_PredictREModel: cluster ids / grouped effects / random coefficients for prediction %s", scope);
-  if (mdl->p_cov > 0 && !mdl->coef_estimated) return set_error("GPB_PredictREModel: the model has covariates but no estimated coefficients");
-  if (mdl->p_cov > 0 && !covariate_data_pred && !use_saved_data) return set_error("No covariate data is provided in 'covariate_data_pred' but the model has linear regression covariates");   // re_model.cpp Predict
-  if (mdl->p_cov == 0 && covariate_data_pred) return set_error("Covariate data is provided in 'covariate_data_pred' but the model has no linear regression covariates");
-  if (mdl->p_cov > 0 && use_saved_data) return set_error("GPB_PredictREModel: saved prediction data together with covariates %s", scope);
-  const bool cond_all = mdl->vecchia_pred_type == "order_obs_first_cond_all";
-  const bool pred_first = mdl->vecchia_pred_type == "order_pred_first";
-  const bool latent_all = mdl->vecchia_pred_type == "latent_order_obs_first_cond_all";
-  const bool latent = latent_all || mdl->vecchia_pred_type == "latent_order_obs_first_cond_obs_only";
-  if (mdl->vecchia_pred_type != "order_obs_first_cond_obs_only" && !cond_all && !pred_first && !latent)
-    return set_error("GPB_PredictREModel: vecchia_pred_type '%s' %s", mdl->vecchia_pred_type.c_str(), scope);
-  const double* cp = gp_coords_data_pred;
-  int np = num_data_pred;
-  if (use_saved_data) { cp = mdl->coords_pred.empty() ? nullptr : mdl->coords_pred.data(); np = mdl->num_data_pred; }
-  if (!cp || np <= 0) return set_error("GPB_PredictREModel: no coordinates for prediction (gp_coords_data_pred / GPB_SetPredictionData)");
-  double tr[3];
-  if (cov_pars) { double c3[3] = {cov_pars[0], cov_pars[1], cov_pars[2]}; if (transform_cov_pars(mdl, c3, tr)) return -1; }
-  else {
-    if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");   // re_model.cpp:1119-1121
-    std::copy(mdl->cov_pars_tr, mdl->cov_pars_tr + 3, tr);
-  }
-  // response and offset (SetYCalcCovCalcYAuxForPred, re_model_template.h:11141-11166): with an offset -- the argument, else the one saved by
-  // GPB_SetOffsetData (:3601-3607) -- the residual (y_obs or the stored response) minus the offset becomes the response
-  if (!y_data && !mdl->y_set) return set_error("GPB_PredictREModel: y_data is NULL and no response has been set by an earlier call");
-  const double* fe = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-  if (prediction_response(mdl, y_data, fe)) return -1;   // y_obs, else y_vec_ = the response as it was passed in (NOT y - offset of the fit)
-  if (mdl->p_cov > 0 && gpb_hip_vecchia_set_resid(mdl->vh, mdl->beta.data())) return shim_error();   // resid -= X beta (:11150-11152); the host copy for 'cond_all' below
-  std::vector<double> resid_v;                          // response the prediction conditions on, Vecchia order
-  const double* yv = mdl->ybuf;
-  if (mdl->p_cov > 0) {
-    resid_v.assign(mdl->ybuf, mdl->ybuf + mdl->n);
-    for (int j = 0; j < mdl->p_cov; ++j) for (int k = 0; k < mdl->n; ++k) resid_v[k] -= mdl->X[(size_t)j * mdl->n + mdl->perm[k]] * mdl->beta[j];
-    yv = resid_v.data();
-  }
-  auto add_linear_predictor = [&](double* mean) {       // mu += X_pred beta (:3868-3880) and the external fixed effects (:3862-3867)
-    if (mdl->p_cov > 0) for (int j = 0; j < mdl->p_cov; ++j) for (int k = 0; k < np; ++k) mean[k] += covariate_data_pred[(size_t)j * np + k] * mdl->beta[j];
-    if (fixed_effects_pred) for (int k = 0; k < np; ++k) mean[k] += fixed_effects_pred[k];
-  };
-  mdl->yaux_valid = false;
-  // num_neighbors_pred: default 2 * num_neighbors (:299), at most the number of observed points (Vecchia_utils.cpp:755-758) and the
-  // device kernels' GPB_MAX_NEIGHBORS
-  int nnp = mdl->num_neighbors_pred > 0 ? mdl->num_neighbors_pred : 2 * mdl->num_neighbors;
-  if (nnp > mdl->n) nnp = mdl->n;
-  if (nnp > 126) {
-    log_info("[GPBoost-AMD] [Warning] num_neighbors_pred = %d exceeds the %d neighbours the MI355X kernels support; %d are used\n", nnp, 126, 126);
-    nnp = 126;
-  }
-  if (cond_all) {
-    // 'order_obs_first_cond_all': search + factor of the appended rows on the device, then the forward substitution with Bp and the rows
-    // of Bp^-1 on the host (Vecchia_utils.cpp:2061-2090); y of the observed points in Vecchia order is the resident response
-    if (nnp > mdl->n + np - 1) nnp = mdl->n + np - 1;
-    if (nnp > 126) nnp = 126;
-    int mu = 0;
-    std::vector<int32_t> nnp_rows((size_t)np * nnp);
-    std::vector<double> Ap((size_t)np * nnp), Dp(np);
-    if (gpb_hip_vecchia_predict_cond_all(mdl->vh, np, cp, nnp, mdl->cov_type, tr[1], tr[2], &mu, nnp_rows.data(), Ap.data(), Dp.data(), nullptr)) return shim_error();
-    if (GPB_HIP_PredictCondAllHost(mdl->n, np, mu, nnp_rows.data(), Ap.data(), Dp.data(), yv, tr[0], predict_response, out_predict,
-                                   predict_var ? out_predict + np : nullptr, predict_cov_mat ? out_predict + np : nullptr)) return -1;
-    add_linear_predictor(out_predict);
-    return 0;
-  }
-  if (pred_first || latent) {
-    // 'order_pred_first' (CalcPredVecchiaPredictedFirstOrder, Vecchia_utils.cpp:2203-2444) and 'latent_order_obs_first_cond_*'
-    // (CalcPredVecchiaLatentObservedFirstOrder, :2446-2666): neighbour search + factor of EVERY point of the joint ordering on the device; the
-    // conditional precision is assembled here from the factor rows and solved / inverted by the dense Cholesky on the device.
-    //   order_pred_first: cond_prec = Bp' Dp^-1 Bp + Bop' Do^-1 Bop over the prediction points, mean = -cond_prec^-1 Bop' Do^-1 Bo y (:2419-2423)
-    //   latent_*: the reference forms Sigma = B^-1 D B^-T and conditions on y = b_obs + eps by the Woodbury identity (:2597-2650); the same
-    //     posterior is M^-1 Z_o' R^-1 y and M^-1 restricted to the prediction points with M = B' D^-1 B + Z_o' R^-1 Z_o, which needs no B^-1
-    const int n = mdl->n, n_all = n + np;
-    const char* dense_scope = "is not on the MI355X path of this library (the conditional precision is handled densely; use 'order_obs_first_cond_obs_only' / 'order_obs_first_cond_all')";
-    if (pred_first && np > 24000) return set_error("GPB_PredictREModel: 'order_pred_first' for %d > 24000 prediction points %s", np, dense_scope);
-    if (latent && n_all > 24000) return set_error("GPB_PredictREModel: '%s' for %d > 24000 observed + prediction points %s", mdl->vecchia_pred_type.c_str(), n_all, dense_scope);
-    const int mcap = (pred_first || latent_all) ? n_all - 1 : n;
-    if (nnp > mcap) nnp = mcap;
-    std::vector<int32_t> nn((size_t)n_all * nnp);
-    std::vector<double> A((size_t)n_all * nnp), D(n_all), u(n_all);
-    int mu = 0, dup = 0;
-    if (gpb_hip_vecchia_predict_joint_factor(mdl->vh, np, cp, nnp, pred_first ? 1 : 0, (pred_first || latent_all) ? 1 : 0, latent ? 0 : 1, mdl->cov_type,
-                                             tr[1], tr[2], &mu, nn.data(), A.data(), D.data(), u.data(), &dup)) return shim_error();
-    if (latent && dup) return set_error("Duplicates found among training and test coordinates. This is not supported for predictions with a Vecchia approximation for the latent process ('latent_') ");   // :2563-2566
-    const bool need_cov = predict_var || predict_cov_mat;
-    const int q = pred_first ? np : n_all;                  // dimension of the precision matrix
-    const int col_end = pred_first ? np : n_all;            // columns of B that enter it
-    std::vector<double> M((size_t)q * q, 0.), rhs(q, 0.), x(q), inv;
-    std::vector<int> ec; std::vector<double> ev;
-    ec.reserve(mu + 1); ev.reserve(mu + 1);
-    for (int i = 0; i < n_all; ++i) {
-      ec.clear(); ev.clear();
-      if (i < col_end) { ec.push_back(i); ev.push_back(1.); }
-      for (int j = 0; j < mu; ++j) {
-        const int c = nn[(size_t)i * mu + j];
-        if (c >= 0 && c < col_end) { ec.push_back(c); ev.push_back(-A[(size_t)i * mu + j]); }
-      }
-      const double dinv = 1. / D[i];
-      for (size_t a1 = 0; a1 < ec.size(); ++a1) {
-        const double va = ev[a1] * dinv;
-        for (size_t b1 = 0; b1 < ec.size(); ++b1) if (ec[b1] <= ec[a1]) M[(size_t)ec[a1] * q + ec[b1]] += va * ev[b1];      // lower triangle
-        if (pred_first && i >= np) rhs[ec[a1]] -= va * u[i];                                                                 // -Bop' Do^-1 (Bo y)
-      }
-    }
-    if (latent) for (int k = 0; k < n; ++k) {               // + Z_o' R^-1 Z_o and the right-hand side Z_o' R^-1 y, R^-1 = diag(w) (:2502-2506)
-      const double w = mdl->has_weights ? 1. / mdl->nug_v[k] : 1.;
-      M[(size_t)k * q + k] += w;
-      rhs[k] = w * yv[k];
-    }
-    const int sub0 = pred_first ? 0 : n;
-    if (need_cov) inv.resize((size_t)np * np);
-    if (gpb_hip_dense_spd_solve(q, M.data(), rhs.data(), x.data(), sub0, need_cov ? inv.data() : nullptr)) return shim_error();
-    for (int k = 0; k < np; ++k) out_predict[k] = x[sub0 + k];
-    add_linear_predictor(out_predict);
-    // latent types: the error variance is ADDED for the response (:2624-2626, 2645-2647); 'order_pred_first' has it in the factor and it is
-    // REMOVED for the latent process (re_model_template.h:4134-4150)
-    const double dshift = latent ? (predict_response ? 1. : 0.) : (predict_response ? 0. : -1.);
-    if (predict_var) for (int k = 0; k < np; ++k) out_predict[np + k] = tr[0] * (inv[(size_t)k * np + k] + dshift);
-    if (predict_cov_mat) {
-      for (size_t k = 0; k < (size_t)np * np; ++k) out_predict[np + k] = tr[0] * inv[k];
-      for (int k = 0; k < np; ++k) out_predict[np + (size_t)k * np + k] += tr[0] * dshift;
-    }
-    return 0;
-  }
-  std::vector<double> D(np);
-  if (gpb_hip_vecchia_predict_obs_only(mdl->vh, np, cp, nnp, mdl->cov_type, tr[1], tr[2], out_predict, D.data(), nullptr)) return shim_error();
-  add_linear_predictor(out_predict);
-  if (predict_var)
-    for (int k = 0; k < np; ++k) out_predict[np + k] = tr[0] * (predict_response ? D[k] : D[k] - 1.);
-  if (predict_cov_mat) {                       // neighbours are observed points only: Bp = I, the predictive covariance is diag(Dp)
-    std::fill(out_predict + np, out_predict + np + (size_t)np * np, 0.);
-    for (int k = 0; k < np; ++k) out_predict[np + (size_t)k * np + k] = tr[0] * (predict_response ? D[k] : D[k] - 1.);
-  }
-  C_API_END();
-}
+// prediction: GPB_SetPredictionData, GPB_PredictREModel, GPB_PredictREModelTrainingDataRandomEffects, GPB_HIP_PredictCondAllHost
+#include "gpb_predict.inc"
+
+extern "C" {
 
 int GPB_GetCurrentNegLogLikelihood(REModelHandle handle, double* negll) {
   C_API_BEGIN();
@@ -3058,91 +2450,6 @@ int GPB_GetInitAuxPars(REModelHandle handle, double* aux_pars) {
   if (!mdl) return set_error("GPB_GetInitAuxPars: null handle");
   if (mdl->num_aux > 0 && aux_pars) for (int j = 0; j < mdl->num_aux; ++j) aux_pars[j] = mdl->init_aux_given ? mdl->init_aux[j] : -1.;      // re_model.cpp:1423-1434: -1 = found internally
   return 0;
-}
-
-/* PredictTrainingDataRandomEffects (re_model.cpp:1217-1275, re_model_template.h:4455-4514): posterior mean of the latent GP at the
-   training locations, Gaussian Vecchia model: b^ = (y - F) - y_aux with y_aux = Psi^-1 (y - F) (:4502-4505); with calc_var the second n
-   entries of out_predict are sigma2 (1 - diag(Psi^-1)) (:4508-4514). */
-int GPB_PredictREModelTrainingDataRandomEffects(REModelHandle handle, const double* cov_pars_pred, const double* y_obs, double* out_predict,
-                                                const double* fixed_effects, bool calc_var) {
-  C_API_BEGIN();
-  auto* mdl = reinterpret_cast<REModelHip*>(handle);
-  if (!mdl || !out_predict) return set_error("GPB_PredictREModelTrainingDataRandomEffects: null argument");
-  // re_model.cpp / re_model_template.h: the reference refuses this call for the approximation, Gaussian or not -- the same words
-  if (mdl && mdl->vif) return set_error("PredictTrainingDataRandomEffects() is currently not implemented for the 'full_scale_vecchia' approximation. Call the predict() function instead ");
-  if (mdl->likelihood != "gaussian") {
-    // non-Gaussian Vecchia models (re_model_template.h:4683-4725): the mode of the latent process, mapped to the data by random_effects_indices_of_data_
-    // if locations repeat, and -- calc_var -- diag((Sigma^-1 + W)^-1) (CalcVarLaplaceApproxVecchia): exact, one block solve per 52 random effects
-    if (mdl->eh || mdl->vhs.size() != 1) return set_error("GPB_PredictREModelTrainingDataRandomEffects: this model is not on the MI355X path of this library");
-    double s12, rho;
-    if (cov_pars_pred) { s12 = cov_pars_pred[0]; rho = cov_pars_pred[1]; }
-    else {
-      if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");   // re_model.cpp:1238-1240
-      s12 = mdl->cov_pars_tr[0]; rho = range_const(mdl) / mdl->cov_pars_tr[1];
-    }
-    if (!(s12 > 0.) || !(rho > 0.)) return set_error("Covariance parameters need to be positive (found %g, %g)", s12, rho);
-    const double* fel = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);
-    std::vector<double> fe_lin;                  // + X beta of a model fitted with covariates
-    if (mdl->p_cov > 0 && mdl->coef_estimated) {
-      fe_lin.assign(mdl->n, 0.);
-      for (int i = 0; i < mdl->n; ++i) { double v = fel ? fel[i] : 0.; for (int j = 0; j < mdl->p_cov; ++j) v += mdl->X[(size_t)j * mdl->n + i] * mdl->beta[j]; fe_lin[i] = v; }
-      fel = fe_lin.data();
-    }
-    if (y_obs) { if (laplace_upload_data(mdl, y_obs, fel)) return -1; }
-    else {
-      if (!mdl->y_set) return set_error("Response variable data is not provided and has not been set before");   // :4473-4477
-      if (laplace_upload_fixed_effects(mdl, fel)) return -1;
-    }
-    const int nr = mdl->n_re > 0 ? mdl->n_re : mdl->n;
-    if (calc_var && nr > 20000) return set_error("GPB_PredictREModelTrainingDataRandomEffects: variances for %d random effects of a non-Gaussian model (one block solve per 52 of them; limit 20000)", nr);
-    std::vector<double> mode(nr), var(calc_var ? nr : 0);
-    if (laplace_prepare_preconditioner(mdl)) return -1;
-    if (gpb_hip_vecchia_laplace_logit(mdl->vh, mdl->cov_type, s12, range_const(mdl) / rho, mdl->num_rand_vec_trace, mdl->seed_rand_vec_trace, mdl->cg_max_num_it,
-                                      mdl->cg_max_num_it_tridiag, mdl->cg_delta_conv, mdl->delta_conv_mode_finding, 1, mdl->lap_info, mode.data()))
-      return shim_error();
-    if (calc_var && gpb_hip_vecchia_laplace_mode_var(mdl->vh, mdl->cg_max_num_it, kPredVarCgTol, var.data(), nullptr)) return shim_error();
-    for (int k = 0; k < mdl->n; ++k) {
-      const int r = mdl->n_re > 0 ? mdl->re_of[k] : k;
-      out_predict[mdl->perm[k]] = mode[r];
-      if (calc_var) out_predict[(size_t)mdl->n + mdl->perm[k]] = var[r];
-    }
-    return 0;
-  }
-  double cp[3];
-  if (cov_pars_pred) std::copy(cov_pars_pred, cov_pars_pred + 3, cp);
-  else {
-    if (!mdl->cov_pars_initialized) return set_error("Covariance parameters have not been estimated or are not given.");   // re_model.cpp:1238-1240
-    transform_back(mdl, mdl->cov_pars_tr, cp);
-  }
-  const double* fe = fixed_effects ? fixed_effects : (mdl->has_offset ? mdl->offset.data() : nullptr);   // :4486-4492
-  std::vector<double> yc(mdl->n), ya(mdl->n);
-  if (y_obs) { for (int i = 0; i < mdl->n; ++i) yc[i] = y_obs[i] - (fe ? fe[i] : 0.); }
-  else {
-    if (!mdl->y_set) return set_error("Response variable data is not provided and has not been set before");   // :4473-4477
-    for (int i = 0; i < mdl->n; ++i) yc[i] = mdl->y_host[i] - (fe ? fe[i] : 0.);   // y_vec_ - fixed effects (:11143-11160)
-  }
-  {
-    std::vector<double> y_keep;                   // yc is a residual, not a response: y_vec_ stays what the caller passed in last
-    if (!y_obs) y_keep.swap(mdl->y_host);
-    const int rc = GPB_HIP_CalcYAux(handle, yc.data(), cp, ya.data());
-    if (!y_obs) mdl->y_host.swap(y_keep); else mdl->y_host.assign(y_obs, y_obs + mdl->n);
-    if (rc) return -1;
-  }
-  for (int i = 0; i < mdl->n; ++i) out_predict[i] = yc[i] - ya[i];
-  if (calc_var && mdl->eh) {   // exact GP: Cov[b | y] = Sigma - Sigma Psi^-1 Sigma = sigma2 (I - Psi_t^-1) (the dense branch's M_aux products, :4515-4620)
-    double trx[3];
-    if (transform_cov_pars(mdl, cp, trx)) return -1;
-    std::vector<double> dg(mdl->n);
-    if (gpb_hip_exact_psi_inv_diag(mdl->eh, mdl->cov_type, trx[1], trx[2], dg.data())) return shim_error();
-    for (int k = 0; k < mdl->n; ++k) out_predict[mdl->n + mdl->perm[k]] = cp[0] * (1. - dg[k]);
-  } else if (calc_var) {      // :4508-4514: sigma2 (1 - column sums of B o (D^-1 B)) = sigma2 (1 - diag(B' D^-1 B)); the factor of CalcYAux is resident
-    std::vector<double> dg(mdl->n);
-    for (size_t c = 0; c < mdl->vhs.size(); ++c)
-      if (gpb_hip_vecchia_psi_inv_diag(mdl->vhs[c], dg.data() + mdl->cl_off[c])) return shim_error();
-    for (int k = 0; k < mdl->n; ++k) out_predict[mdl->n + mdl->perm[k]] = cp[0] * (1. - dg[k]);
-    mdl->yaux_valid = false;                            // the diagonal pass used the y_aux scratch vector
-  }
-  C_API_END();
 }
 
 int GPB_HIP_EvalNegLogLikelihoodAndGrad(REModelHandle handle, const double* y_data, double* cov_pars,

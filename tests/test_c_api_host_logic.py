@@ -80,6 +80,14 @@ def test_vecchia_response_preconditioner_on_the_cpu_restatement_of_the_shim(mock
     assert "16 passed" in tail, tail      # (5 values + 3 oracle-step cases + 5 model-surface cases + 2 with weights / repeated locations + the generality kernel's shapes)
 
 
+def test_predictions_return_the_recorded_bits_and_messages_on_the_cpu_restatement_of_the_shim(mock_lib):
+    """The prediction host code (gpb_predict.inc) against tests/golden/predict_paths_mock.npz: every number by its bit pattern, every refusal by its words, as this
+    shim returned them before GPB_PredictREModel was split (tests/test_zz_predict_paths_gpu.py; the cases of the exact GP, inducing points and sample weights run on the
+    device only and pass trivially here)."""
+    tail = _run_gpu_tests_on_the_mock(mock_lib, ["test_zz_predict_paths_gpu.py"])
+    assert "19 passed" in tail, tail      # (the coverage check + 18 cases)
+
+
 ROUTE_A_DRIVER = r'''
 import json, sys, types
 sys.modules.setdefault("optuna", types.ModuleType("optuna"))       # optional dependency of the reference's package, absent here
