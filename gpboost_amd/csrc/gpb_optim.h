@@ -16,7 +16,11 @@
 //   LBFGSSolver::minimize                     external_libs/LBFGSpp/include/LBFGS.h:86-300 (GPBoost's modified copy)
 //   LineSearchBacktracking::LineSearch        external_libs/LBFGSpp/include/LBFGSpp/LineSearchBacktracking.h:44-143
 //   BFGSMat::add_correction / apply_Hv        external_libs/LBFGSpp/include/LBFGSpp/BFGSMat.h:89-186
+//   OptimLib's Nelder-Mead                     external_libs/OptimLib/unconstrained/nm.hpp:95-372
 // The parameter vector is the reference's TRANSFORMED one (re_model.cpp:301-318): theta = (sigma2, sigma1_2 / sigma2, a).
+// gpb_optim.cpp holds each of these once -- BfgsMat, lbfgs_minimize (+ line_search_backtracking), nelder_mead, spd_inverse_diagonal -- followed by one part per
+// model family (Gaussian: State; Laplace: LapState; coefficients / auxiliary parameters: LapCoefState) with that family's gradient descent and its small adapter
+// for lbfgs_minimize, and by the entry points declared here.
 #ifndef GPB_OPTIM_H_
 #define GPB_OPTIM_H_
 
@@ -79,12 +83,13 @@ int gpb_optimize_gaussian_cov_pars(const GpbOptimConfig& cfg, int num_data, gpb_
 //   + 16      first_update: the reference divides cg_max_num_it(_tridiag) by 3 in the first gradient-descent update (likelihoods.h:3833-3836)
 typedef int (*gpb_laplace_fn)(void* ctx, int op, double var, double a, double* out3);
 
-struct GpbLaplaceOptimResult {
+struct GpbLaplaceFitResult {                // what every fit of a non-Gaussian model returns
   double theta[2];
   int num_it = 0;
   double negll = 0.;
   int num_evals = 0;
 };
+typedef GpbLaplaceFitResult GpbLaplaceOptimResult, GpbLaplaceCoefResult, GpbLaplaceAuxResult;     // the names the callers use
 
 int gpb_optimize_laplace_cov_pars(const GpbOptimConfig& cfg, gpb_laplace_fn fn, void* ctx, const double theta_init[2],
                                   GpbLaplaceOptimResult* out, char* err, int errlen);
@@ -108,13 +113,6 @@ int gpb_laplace_std_errors(gpb_laplace_fn fn, void* ctx, const double theta[2], 
 //   op 2      gradient and grad_F of the CURRENT state; op 3 reset the mode to its previous value; op 4 forget the mode
 typedef int (*gpb_laplace_fe_fn)(void* ctx, int op, double var, double a, const double* fixed_effects, double* out3, double* grad_F);
 
-struct GpbLaplaceCoefResult {
-  double theta[2];
-  int num_it = 0;
-  double negll = 0.;
-  int num_evals = 0;
-};
-
 // X_scaled: column-major n x p (already centred / scaled where the reference does so); offset: n values added to X beta (NULL: none);
 // beta: in = initial values, out = estimates (both on the scaled covariates); C_mu, C_sigma2: FindConstantsCapTooLargeLearningRateCoef.
 // learn_cov = false: the covariance parameters stay at theta_init and only beta is in the lbfgs vector (learn_cov_aux_pars = false: the fit of
@@ -131,13 +129,6 @@ int gpb_optimize_laplace_coef_cov_pars(const GpbOptimConfig& cfg, gpb_laplace_fe
 //             (log var, log a) and out[3 .. 3 + naux) = gradient wrt log aux
 //   op 2      gradient of the CURRENT state; op 3 reset the mode to its previous value; op 4 forget the mode
 typedef int (*gpb_laplace_aux_fn)(void* ctx, int op, double var, double a, const double* aux, int naux, double* out);
-
-struct GpbLaplaceAuxResult {
-  double theta[2];
-  int num_it = 0;
-  double negll = 0.;
-  int num_evals = 0;
-};
 
 // aux: in = initial values, out = estimates (original scale).  Only optimizer_cov = "lbfgs" (the reference's default).
 int gpb_optimize_laplace_cov_aux_pars(const GpbOptimConfig& cfg, gpb_laplace_aux_fn fn, void* ctx, int naux, const double theta_init[2], double* aux,
