@@ -15,6 +15,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <atomic>
@@ -128,6 +130,12 @@ int check_device() {
   if (e != hipSuccess || cnt <= 0)
     return fail("no HIP device available (%s): the gfx950 hot path has no CPU fallback", e != hipSuccess ? hipGetErrorString(e) : "device count 0");
   return 0;
+}
+
+// the covariance arguments of every entry point that evaluates a covariance function
+int check_cov_type(int cov_type) { return cov_type < 0 || cov_type > 2 ? fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type) : 0; }
+int check_cov_args(int cov_type, double var, double a) {
+  return check_cov_type(cov_type) ? -1 : var > 0. && a > 0. ? 0 : fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
 }
 
 std::vector<double> exp_table() {
@@ -453,6 +461,63 @@ struct gpb_hip_hist {
   std::vector<int> tree_node_is_cat; std::vector<unsigned> tree_node_cat_bits;   // last tree: per node, is the split categorical / the 8 words of its set of bins
 };
 
+// column-major n x d coordinates -> the kernels' records {x0, x1, x2, 0} (the coordinates beyond the third travel in d_coords_nd)
+static std::vector<double4> pack_points(const double* coords_colmajor, int n, int d) {
+  std::vector<double4> pts(n);
+  for (int i = 0; i < n; ++i) pts[i] = make_double4(coords_colmajor[i], d > 1 ? coords_colmajor[(size_t)n + i] : 0.0, d > 2 ? coords_colmajor[(size_t)2 * n + i] : 0.0, 0.0);
+  return pts;
+}
+
+// What one neighbour search looks for: start_at, end_search_at as find_nearest_neighbors_Vecchia_fast takes them (Vecchia_utils.cpp:739-754); the positions
+// (coordinate-sum order) [pos0, pos1) of this launch; the byte the table is filled with first (-1: none); whether n == 1 is one -1 column without a launch
+struct NNSearch { int start_at = 0, end_search_at = 0, pos0 = 0, pos1 = 0, prefill = -1; bool single_point_shortcut = false; };
+
+// The one neighbour search.  coords: the column-major s->n x s->d coordinates of the state s, whose d_pts, d_coords_nd, d_flag and stream it uses and whose
+// d_nn it fills.  Coordinate sums and their argsort on the host exactly as Vecchia_utils.cpp:774-786 does.  The caller sets its handle flags afterwards.
+static int search_neighbors(gpb_hip_vecchia* s, const double* coords, const NNSearch& q, int* has_duplicates) {
+  const int n = s->n, d = s->d, m = s->m;
+  std::vector<double> csum(n);
+  for (int i = 0; i < n; ++i) { double sum = coords[i]; for (int c = 1; c < d; ++c) sum += coords[(size_t)c * n + i]; csum[i] = sum; }
+  std::vector<int> sort_sum(n);
+  std::iota(sort_sum.begin(), sort_sum.end(), 0);
+  const double* v = csum.data();
+  std::sort(sort_sum.begin(), sort_sum.end(), [v](int i1, int i2) { return v[i1] < v[i2]; });
+  std::vector<double4> rec(n);
+  for (int k = 0; k < n; ++k) { const int i = sort_sum[k]; rec[k] = make_double4(coords[i], d > 1 ? coords[(size_t)n + i] : 0.0, d > 2 ? coords[(size_t)2 * n + i] : 0.0, csum[i]); }
+  double4* d_rec = nullptr; int* d_idx = nullptr; double* d_rec_nd = nullptr; int* d_qorder = nullptr;
+  const auto free_tmp = scope_exit([&] { (void)hipFree(d_rec); (void)hipFree(d_idx); (void)hipFree(d_qorder); (void)hipFree(d_rec_nd); });
+  HIP_OK(hipMalloc(&d_rec, sizeof(double4) * (size_t)n));
+  HIP_OK(hipMalloc(&d_idx, sizeof(int) * (size_t)n));
+  HIP_OK(hipMemcpyAsync(d_rec, rec.data(), sizeof(double4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  std::vector<double> rec_nd;
+  if (d > 3) {
+    rec_nd.resize((size_t)n * (d + 1));
+    for (int k = 0; k < n; ++k) for (int c = 0; c <= d; ++c) rec_nd[(size_t)k * (d + 1) + c] = c < d ? coords[(size_t)c * n + sort_sum[k]] : csum[sort_sum[k]];
+    HIP_OK(hipMalloc(&d_rec_nd, sizeof(double) * rec_nd.size()));
+    HIP_OK(hipMemcpyAsync(d_rec_nd, rec_nd.data(), sizeof(double) * rec_nd.size(), hipMemcpyHostToDevice, s->stream));
+  }
+  HIP_OK(hipMemcpyAsync(d_idx, sort_sum.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+  HIP_OK(hipMemsetAsync(s->d_flag, 0, sizeof(int), s->stream));
+  gpb::NNKernelArgs a;
+  a.sorted_rec = d_rec; a.sorted_idx = d_idx; a.pts = s->d_pts; a.nn = s->d_nn; a.has_duplicates = s->d_flag; a.n = n; a.m = m;
+  a.sorted_nd = d_rec_nd; a.coords_nd = s->d_coords_nd;
+  a.start_at = q.start_at; a.end_search_at = q.end_search_at; a.pos0 = q.pos0; a.pos1 = q.pos1;
+  std::vector<int> qorder((size_t)std::max(std::min(q.pos1 - q.pos0, n - q.start_at), 1));
+  int nq = 0;
+  gpb::nn_query_order(sort_sum.data(), q.pos0, q.pos1, m, q.start_at, qorder.data(), &nq);     // the order in which the lanes take the queries (nn_kernels.h)
+  HIP_OK(hipMalloc(&d_qorder, sizeof(int) * qorder.size()));
+  HIP_OK(hipMemcpyAsync(d_qorder, qorder.data(), sizeof(int) * (size_t)std::max(nq, 1), hipMemcpyHostToDevice, s->stream));
+  a.qorder = d_qorder; a.nq = nq;
+  if (q.prefill >= 0) HIP_OK(hipMemsetAsync(s->d_nn, q.prefill, sizeof(int) * (size_t)n * m, s->stream));
+  if (q.single_point_shortcut && n == 1) HIP_OK(hipMemsetAsync(s->d_nn, 0xff, sizeof(int) * (size_t)n * m, s->stream));
+  else HIP_OK(gpb::launch_vecchia_nn(d, a, s->stream));
+  int flag = 0;
+  HIP_OK(hipMemcpyAsync(&flag, s->d_flag, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_OK(hipStreamSynchronize(s->stream));
+  if (has_duplicates) *has_duplicates = flag;
+  return 0;
+}
+
 extern "C" {
 
 const char* gpb_hip_get_last_error(void) { return g_err; }
@@ -566,13 +631,7 @@ int gpb_hip_vecchia_create(int32_t n, int32_t d, int32_t num_neighbors, const do
   h->coords.assign(coords_colmajor, coords_colmajor + (size_t)n * d);
   HIP_OK(hipGetDevice(&h->device));
   HIP_OK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  std::vector<double4> pts(n);
-  for (int i = 0; i < n; ++i) {
-    pts[i].x = coords_colmajor[i];
-    pts[i].y = d > 1 ? coords_colmajor[(size_t)n + i] : 0.0;
-    pts[i].z = d > 2 ? coords_colmajor[(size_t)2 * n + i] : 0.0;
-    pts[i].w = 0.0;
-  }
+  const std::vector<double4> pts = pack_points(coords_colmajor, n, d);
   HIP_OK(hipMalloc(&h->d_pts, sizeof(double4) * 2 * (size_t)n));      // (second half: the spatially sorted copy the neighbour gathers read, sorted_gather_prepare)
   HIP_OK(hipMemcpy(h->d_pts, pts.data(), sizeof(double4) * (size_t)n, hipMemcpyHostToDevice));
   if (d > 3) {       // generality path: row-major coordinates for the LDS-resident point kernel and the d-dimensional neighbour search
@@ -639,68 +698,13 @@ int gpb_hip_vecchia_sync(gpb_hip_vecchia_t* h) {
 // range is not the whole table (multi-GPU: one block of positions per rank, merged by a max-all-reduce -- a valid entry is >= -1).
 static int find_neighbors_impl(gpb_hip_vecchia_t* h, int part, int nparts, int* has_duplicates) {
   HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, d = h->d, m = h->m;
-  // coordinate sums and their argsort, on the host exactly as Vecchia_utils.cpp:774-786 does
-  std::vector<double> csum(n);
-  for (int i = 0; i < n; ++i) {
-    double s = h->coords[i];
-    for (int c = 1; c < d; ++c) s += h->coords[(size_t)c * n + i];
-    csum[i] = s;
-  }
-  std::vector<int> sort_sum(n);
-  std::iota(sort_sum.begin(), sort_sum.end(), 0);
-  const double* v = csum.data();
-  std::sort(sort_sum.begin(), sort_sum.end(), [v](int i1, int i2) { return v[i1] < v[i2]; });
-  std::vector<double4> rec(n);
-  for (int k = 0; k < n; ++k) {
-    const int i = sort_sum[k];
-    rec[k].x = h->coords[i];
-    rec[k].y = d > 1 ? h->coords[(size_t)n + i] : 0.0;
-    rec[k].z = d > 2 ? h->coords[(size_t)2 * n + i] : 0.0;
-    rec[k].w = csum[i];
-  }
-  double4* d_rec = nullptr; int* d_idx = nullptr; double* d_rec_nd = nullptr; int* d_qorder = nullptr;
-  const auto free_tmp = scope_exit([&] { (void)hipFree(d_rec); (void)hipFree(d_idx); (void)hipFree(d_qorder); (void)hipFree(d_rec_nd); });
-  HIP_OK(hipMalloc(&d_rec, sizeof(double4) * (size_t)n));
-  HIP_OK(hipMalloc(&d_idx, sizeof(int) * (size_t)n));
-  HIP_OK(hipMemcpyAsync(d_rec, rec.data(), sizeof(double4) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  std::vector<double> rec_nd;
-  if (d > 3) {
-    rec_nd.resize((size_t)n * (d + 1));
-    for (int k = 0; k < n; ++k) {
-      const int i = sort_sum[k];
-      for (int c = 0; c < d; ++c) rec_nd[(size_t)k * (d + 1) + c] = h->coords[(size_t)c * n + i];
-      rec_nd[(size_t)k * (d + 1) + d] = csum[i];
-    }
-    HIP_OK(hipMalloc(&d_rec_nd, sizeof(double) * rec_nd.size()));
-    HIP_OK(hipMemcpyAsync(d_rec_nd, rec_nd.data(), sizeof(double) * rec_nd.size(), hipMemcpyHostToDevice, h->stream));
-  }
-  HIP_OK(hipMemcpyAsync(d_idx, sort_sum.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemsetAsync(h->d_flag, 0, sizeof(int), h->stream));
-  gpb::NNKernelArgs a;
-  a.sorted_rec = d_rec; a.sorted_idx = d_idx; a.pts = h->d_pts; a.nn = h->d_nn; a.has_duplicates = h->d_flag; a.n = n; a.m = m;
-  a.sorted_nd = d_rec_nd; a.coords_nd = h->d_coords_nd;
+  const int n = h->n;
+  NNSearch q; q.end_search_at = n - 2; q.single_point_shortcut = true;
   // positions are in coordinate-sum order, i.e. random with respect to the index that decides a query's cost: equal blocks of
   // positions are balanced (SURVEY.md 8e suggested cyclic assignment for index-ordered blocks; not needed here)
-  a.start_at = 0; a.end_search_at = n - 2;
-  a.pos0 = (int)((long long)n * part / nparts); a.pos1 = (int)((long long)n * (part + 1) / nparts);
-  // the order in which the lanes take this block's queries: grouped by index octave quarter (nn_kernels.h)
-  std::vector<int> qorder((size_t)std::max(a.pos1 - a.pos0, 1));
-  int nq = 0;
-  gpb::nn_query_order(sort_sum.data(), a.pos0, a.pos1, m, 0, qorder.data(), &nq);
-  HIP_OK(hipMalloc(&d_qorder, sizeof(int) * qorder.size()));
-  HIP_OK(hipMemcpyAsync(d_qorder, qorder.data(), sizeof(int) * (size_t)std::max(nq, 1), hipMemcpyHostToDevice, h->stream));
-  a.qorder = d_qorder; a.nq = nq;
-  if (nparts > 1) HIP_OK(hipMemsetAsync(h->d_nn, 0x80, sizeof(int) * (size_t)n * m, h->stream));     // 0x80808080 < -1: "not mine"
-  if (n == 1) {
-    HIP_OK(hipMemsetAsync(h->d_nn, 0xff, sizeof(int) * (size_t)n * m, h->stream));
-  } else {
-    HIP_OK(gpb::launch_vecchia_nn(d, a, h->stream));
-  }
-  int flag = 0;
-  HIP_OK(hipMemcpyAsync(&flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (has_duplicates) *has_duplicates = flag;
+  q.pos0 = (int)((long long)n * part / nparts); q.pos1 = (int)((long long)n * (part + 1) / nparts);
+  if (nparts > 1) q.prefill = 0x80;     // 0x80808080 < -1: "not mine"
+  if (search_neighbors(h, h->coords.data(), q, has_duplicates)) return -1;
   h->has_nn = nparts == 1; h->nn_partial = nparts > 1;
   h->has_transpose = false; h->has_levels = false; h->has_factor = false; h->nn_host.clear();
   return 0;
@@ -884,8 +888,7 @@ static int vecchia_launch(gpb_hip_vecchia_t* h, int mode, int cov_type, double v
   if (!h) return fail("null handle");
   if (!h->has_nn) return fail("neighbours have not been determined (call gpb_hip_vecchia_find_neighbors / _set_neighbors)");
   if (!h->has_y) return fail("response data has not been set (call gpb_hip_vecchia_set_y)");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
+  if (check_cov_args(cov_type, var, a)) return -1;
   if (!(a > 1e-20) || !(a < 1e20) || !(var < 1e100)) return fail("covariance parameters out of the supported range (var = %g, transformed range = %g)", var, a);
   HIP_OK(hipSetDevice(h->device));
   gpb::VecchiaKernelArgs k;
@@ -1423,15 +1426,20 @@ int gpb_hip_vecchia_set_resid(gpb_hip_vecchia_t* h, const double* beta_host) {
   API_END();
 }
 
+// buffers of the factor (A, D, u = B y), allocated at its first use
+static int alloc_factor(gpb_hip_vecchia_t* h) {
+  if (h->d_A) return 0;
+  HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)h->n * h->m));
+  HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)h->n));
+  HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)h->n));
+  return 0;
+}
+
 int gpb_hip_vecchia_factor(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int gauss_likelihood) {
   API_BEGIN();
   if (!h) return fail("null handle");
   HIP_OK(hipSetDevice(h->device));
-  if (!h->d_A) {
-    HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)h->n * h->m));
-    HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)h->n));
-    HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)h->n));
-  }
+  if (alloc_factor(h)) return -1;
   h->has_yaux = false;
   if (vecchia_launch(h, gpb::MODE_FACTOR, cov_type, var, a, gauss_likelihood, nullptr, 0)) return -1;
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -1512,6 +1520,26 @@ static int vif_upload_matrix(gpb_hip_vecchia_t* h, int slot, const double* src, 
   return 0;
 }
 
+// The RESIDUAL-process factor of the rows [i_begin, n) of a full-scale Vecchia state whose inducing points are set: Linv (the inverse Cholesky factor of
+// Sigma_m, row-major) goes to the device, the cross-covariances C (dC: their range derivative, or null) and V = C Linv' are computed for ALL rows, then A, D, u.
+// The two settings of the diagonal (vif_grad_sums_impl differentiates the same two):
+// Gaussian, Dp starts at 1 (Vecchia_utils.cpp:1873-1874) and the neighbours' diagonal gets + 1, the nugget (:1952-1960); latent, no nugget, their diagonal x 1 + 1e-10 (:1965-1967).
+static int vif_resid_factor(gpb_hip_vecchia_t* h, int i_begin, const double* Linv_rowmajor, int cov_type, double var, double a, bool latent, double* dC) {
+  const int n = h->n, k = h->vif_k, kq = h->vif_kq;
+  if (alloc_factor(h)) return -1;
+  if (vif_upload_matrix(h, 0, Linv_rowmajor, true)) return -1;                   // V = C Linv'
+  HIP_OK(gpb::launch_vif_crosscov(cov_type, h->d_pts, h->d_ip, 0, n, k, kq, h->d, var, a, h->d_vC, dC, h->stream));
+  HIP_OK(gpb::launch_vif_gemm(h->d_vC, h->d_vM, n, kq, h->d_V, false, h->stream));
+  gpb::VecchiaKernelArgs ka;
+  ka.pts = h->d_pts; ka.nn = h->d_nn; ka.exp_tab = h->d_exp_tab; ka.partials = h->d_vif_part;
+  ka.A = h->d_A; ka.D = h->d_D; ka.u = h->d_u;
+  ka.m = h->m; ka.i_begin = i_begin; ka.i_end = n; ka.var = var; ka.a = a;
+  if (latent) { ka.nugget = 0.0; ka.diag_nn = var;       ka.diag_i = var;       ka.diag_mult = 1.0 + 1e-10; }
+  else        { ka.nugget = 1.0; ka.diag_nn = var + 1.0; ka.diag_i = var + 1.0; ka.diag_mult = 1.0; }
+  HIP_OK(gpb::launch_vif_resid_factor(cov_type, ka, h->d_V, k, kq, h->stream));
+  return 0;
+}
+
 int gpb_hip_vecchia_vif_factor(gpb_hip_vecchia_t* h, int cov_type, double var, double a, const double* Linv_rowmajor, int with_grad, double* out3_host,
                                double* G_host) {
   API_BEGIN();
@@ -1519,28 +1547,14 @@ int gpb_hip_vecchia_vif_factor(gpb_hip_vecchia_t* h, int cov_type, double var, d
   if (h->vif_k < 1) return fail("no inducing points have been set (call gpb_hip_vecchia_vif_set_inducing_points)");
   if (!h->has_nn) return fail("neighbours have not been determined (call gpb_hip_vecchia_find_neighbors / _set_neighbors)");
   if (!h->has_y) return fail("response data has not been set (call gpb_hip_vecchia_set_y)");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
+  if (check_cov_args(cov_type, var, a)) return -1;
   if (h->i_begin != 0 || h->i_end != h->n) return fail("full-scale Vecchia needs the whole factor on this device");
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n, k = h->vif_k, kp = h->vif_kp, kq = h->vif_kq;
-  if (!h->d_A) {
-    HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)n * h->m));
-    HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)n));
-    HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)n));
-  }
   const size_t nk = sizeof(double) * (size_t)n * kq;
   if (with_grad && !h->d_vdC) { HIP_OK(hipMalloc(&h->d_vdC, nk)); HIP_OK(hipMalloc(&h->d_vQdC, nk)); }
   h->has_yaux = false; h->vif_has_grad_inputs = false; h->vif_has_grad_factor = false;
-  if (vif_upload_matrix(h, 0, Linv_rowmajor, true)) return -1;                   // V = C Linv'
-  HIP_OK(gpb::launch_vif_crosscov(cov_type, h->d_pts, h->d_ip, 0, n, k, kq, h->d, var, a, h->d_vC, with_grad ? h->d_vdC : nullptr, h->stream));
-  HIP_OK(gpb::launch_vif_gemm(h->d_vC, h->d_vM, n, kq, h->d_V, false, h->stream));
-  gpb::VecchiaKernelArgs ka;
-  ka.pts = h->d_pts; ka.nn = h->d_nn; ka.exp_tab = h->d_exp_tab; ka.partials = h->d_vif_part;
-  ka.A = h->d_A; ka.D = h->d_D; ka.u = h->d_u;
-  ka.m = h->m; ka.i_begin = 0; ka.i_end = n;
-  ka.var = var; ka.a = a; ka.diag_nn = var + 1.0; ka.diag_i = var + 1.0; ka.nugget = 1.0;
-  HIP_OK(gpb::launch_vif_resid_factor(cov_type, ka, h->d_V, k, kq, h->stream));
+  if (vif_resid_factor(h, 0, Linv_rowmajor, cov_type, var, a, false, with_grad ? h->d_vdC : nullptr)) return -1;
   HIP_OK(gpb::launch_reduce_partials(h->d_vif_part, n, 3, h->d_vout, nullptr, h->stream, nullptr));
   HIP_OK(gpb::launch_vif_spmm(h->d_A, h->d_nn, 0, n, h->m, kq, h->d_vC, h->d_vQ, with_grad ? h->d_vdC : nullptr, with_grad ? h->d_vQdC : nullptr, h->stream));
   HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, kq, h->d_vgpart, h->d_vG, h->stream));
@@ -1572,7 +1586,7 @@ static int vif_grad_sums_impl(gpb_hip_vecchia_t* h, int cov_type, double var, do
   {
   if (!h || !Winv || !Si || !N0 || !negMp1 || !w_host || !sums12_host) return fail("null argument");
   if (h->vif_k < 1 || !h->has_factor || !h->vif_has_grad_inputs) return fail("gpb_hip_vecchia_vif_grad_sums needs gpb_hip_vecchia_vif_factor(with_grad = 1) first");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
+  if (check_cov_type(cov_type)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n, k = h->vif_k, kp = h->vif_kp, kq = h->vif_kq;
   const size_t nk = sizeof(double) * (size_t)n * kq;
@@ -1727,33 +1741,35 @@ int gpb_hip_vecchia_yaux_partial_dev(gpb_hip_vecchia_t* h, double* w_dev) {
   API_END();
 }
 
-// Prediction at new locations, every prediction point conditioning on its nearest OBSERVED points only:
-// CalcPredVecchiaObservedFirstOrder(CondObsOnly = true), src/GPBoost/Vecchia_utils.cpp:1701-2060, Gaussian likelihood.
+// the temporary state of a prediction, freed on every way out of its entry point
+struct VecchiaFree { void operator()(gpb_hip_vecchia_t* p) const { gpb_hip_vecchia_free(p); } };
+using TempVecchia = std::unique_ptr<gpb_hip_vecchia_t, VecchiaFree>;
+
+// Prediction at new locations: CalcPredVecchiaObservedFirstOrder, src/GPBoost/Vecchia_utils.cpp:1701-2060.
 // The reference appends the prediction coordinates to the observed ones, searches neighbours with start_at = n_obs and
-// end_search_at = n_obs - 1 (:1792-1799), and runs the same per-point local factorisation as the likelihood (:1883-1975):
-// pred_mean = A_p y_nn, Dp = 1 + sigma1^2/sigma^2 - A_p c.  Here that is one launch of the neighbour-search kernel and one of
-// vecchia_point_kernel<MODE_FACTOR> over the appended rows (their own response slot is 0, so u = -A_p y_nn).
-// Shared by the two prediction types: temporary state [observed (Vecchia order); prediction], neighbour search for the appended rows
-// only (find_nearest_neighbors_Vecchia_fast with start_at = n_obs and end_search_at = n_obs - 1 [cond_obs_only] or -1 [cond_all],
-// Vecchia_utils.cpp:1792-1822), MODE_FACTOR over the appended rows.  *out_t owns the state (caller frees), *out_m = neighbours used.
-// pred_first / all_rows (the joint orderings of 'order_pred_first' and the 'latent_*' types, Vecchia_utils.cpp:2228-2255, 2517-2561): the
-// prediction points come first / every row of the joint ordering is searched (start_at = 0) and factored, not only the appended ones.
-static int predict_factor_appended(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred,
-                                   bool cond_all, int cov_type, double var, double a, gpb_hip_vecchia_t** out_t, int* out_m, int* has_duplicates,
-                                   int gauss_likelihood = 1, bool pred_first = false, bool all_rows = false, bool do_factor = true) {
-  *out_t = nullptr;
+// end_search_at = n_obs - 1 [cond_obs_only] or -1 [cond_all] (find_nearest_neighbors_Vecchia_fast, :1792-1822), and runs the same per-point
+// local factorisation as the likelihood (:1883-1975): pred_mean = A_p y_nn, Dp = 1 + sigma1^2/sigma^2 - A_p c.  Here that is a temporary
+// state [observed (Vecchia order); prediction], one launch of the neighbour-search kernel and one of vecchia_point_kernel<MODE_FACTOR> over
+// the appended rows (their own response slot is 0, so u = -A_p y_nn).  *out_t owns the state, *out_m = neighbours used.  What a caller asks for:
+//   cond_all: the candidates are the observed AND the preceding prediction points;   latent: no nugget, diagonal x (1 + 1e-10) (:1963-1967);
+//   pred_first / all_rows (the joint orderings of 'order_pred_first' and the 'latent_*' types, :2228-2255, 2517-2561): the prediction points come first /
+//   every row is searched and factored;   factor = false: the caller runs its own factor (full-scale Vecchia: vif_resid_factor)
+struct PredictOpts { bool cond_all = false, latent = false, pred_first = false, all_rows = false, factor = true; };
+static int predict_factor_appended(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred, const PredictOpts& o,
+                                   int cov_type, double var, double a, TempVecchia* out_t, int* out_m, int* has_duplicates) {
+  out_t->reset();
   if (!h || !coords_pred_colmajor) return fail("null argument");
   if (n_pred < 1) return fail("Vecchia prediction: n_pred = %d", n_pred);
   if (!h->has_y) return fail("response data has not been set (call gpb_hip_vecchia_set_y)");
   const int n_obs = h->n, d = h->d, n_all = n_obs + n_pred;
   int m = num_neighbors_pred;
-  const int m_cap = cond_all ? n_all - 1 : n_obs;               // :755-758 with end_search_at = num_data - 2 / n_obs - 1
+  const int m_cap = o.cond_all ? n_all - 1 : n_obs;               // :755-758 with end_search_at = num_data - 2 / n_obs - 1
   if (m > m_cap) m = m_cap;
   if (m < 1 || m > GPB_MAX_NEIGHBORS_BIG) return fail("Vecchia prediction: num_neighbors_pred = %d (1..%d supported)", num_neighbors_pred, GPB_MAX_NEIGHBORS_BIG);
   HIP_OK(hipSetDevice(h->device));
   // [observed (Vecchia order); prediction] as one temporary state; the observed records (coordinates + y) are copied on the device
-  if (pred_first && !(all_rows && cond_all)) return fail("Vecchia prediction: the prediction-first ordering searches and factors every row");
-  const int obs0 = pred_first ? n_pred : 0, pred0 = pred_first ? 0 : n_obs;          // where the two groups start in the joint ordering
+  if (o.pred_first && !(o.all_rows && o.cond_all)) return fail("Vecchia prediction: the prediction-first ordering searches and factors every row");
+  const int obs0 = o.pred_first ? n_pred : 0, pred0 = o.pred_first ? 0 : n_obs;          // where the two groups start in the joint ordering
   std::vector<double> call((size_t)n_all * d);
   for (int c = 0; c < d; ++c) {
     std::copy(h->coords.begin() + (size_t)c * n_obs, h->coords.begin() + (size_t)(c + 1) * n_obs, call.begin() + (size_t)c * n_all + obs0);
@@ -1761,88 +1777,53 @@ static int predict_factor_appended(gpb_hip_vecchia_t* h, int32_t n_pred, const d
   }
   gpb_hip_vecchia_t* t = nullptr;
   if (gpb_hip_vecchia_create(n_all, d, m, call.data(), &t)) return -1;
-  *out_t = t;
+  out_t->reset(t);
   HIP_OK(hipStreamSynchronize(h->stream));
   HIP_OK(hipMemcpy(t->d_pts + obs0, h->d_pts, sizeof(double4) * (size_t)n_obs, hipMemcpyDeviceToDevice));   // pred rows keep y = 0
   t->has_y = true;
-  if (h->d_nug && gauss_likelihood) {      // sample weights: observed neighbours carry 1 / w, prediction points the plain nugget (Vecchia_utils.cpp:1952-1958, 2386-2393); the latent factor has no nugget at all
+  if (h->d_nug && !o.latent) {      // sample weights: observed neighbours carry 1 / w, prediction points the plain nugget (Vecchia_utils.cpp:1952-1958, 2386-2393); the latent factor has no nugget at all
     std::vector<double> ones((size_t)n_pred, 1.0);
     HIP_OK(hipMalloc(&t->d_nug, sizeof(double) * (size_t)n_all));
     HIP_OK(hipMemcpy(t->d_nug + obs0, h->d_nug, sizeof(double) * (size_t)n_obs, hipMemcpyDeviceToDevice));
     HIP_OK(hipMemcpy(t->d_nug + pred0, ones.data(), sizeof(double) * (size_t)n_pred, hipMemcpyHostToDevice));
   }
-  // neighbour search for the appended rows only
-  {
-    std::vector<double> csum(n_all);
-    for (int i = 0; i < n_all; ++i) { double s = call[i]; for (int c = 1; c < d; ++c) s += call[(size_t)c * n_all + i]; csum[i] = s; }
-    std::vector<int> sort_sum(n_all);
-    std::iota(sort_sum.begin(), sort_sum.end(), 0);
-    const double* v = csum.data();
-    std::sort(sort_sum.begin(), sort_sum.end(), [v](int i1, int i2) { return v[i1] < v[i2]; });
-    std::vector<double4> rec(n_all);
-    for (int k = 0; k < n_all; ++k) {
-      const int i = sort_sum[k];
-      rec[k].x = call[i]; rec[k].y = d > 1 ? call[(size_t)n_all + i] : 0.0; rec[k].z = d > 2 ? call[(size_t)2 * n_all + i] : 0.0; rec[k].w = csum[i];
-    }
-    double4* d_rec = nullptr; int* d_idx = nullptr; double* d_rec_nd = nullptr; int* d_qorder = nullptr;
-    const auto free_tmp = scope_exit([&] { (void)hipFree(d_rec); (void)hipFree(d_idx); (void)hipFree(d_qorder); (void)hipFree(d_rec_nd); });
-    HIP_OK(hipMalloc(&d_rec, sizeof(double4) * (size_t)n_all));
-    HIP_OK(hipMalloc(&d_idx, sizeof(int) * (size_t)n_all));
-    HIP_OK(hipMemcpyAsync(d_rec, rec.data(), sizeof(double4) * (size_t)n_all, hipMemcpyHostToDevice, t->stream));
-    std::vector<double> rec_nd;
-    if (d > 3) {
-      rec_nd.resize((size_t)n_all * (d + 1));
-      for (int k = 0; k < n_all; ++k) {
-        const int i = sort_sum[k];
-        for (int c = 0; c < d; ++c) rec_nd[(size_t)k * (d + 1) + c] = call[(size_t)c * n_all + i];
-        rec_nd[(size_t)k * (d + 1) + d] = csum[i];
-      }
-      HIP_OK(hipMalloc(&d_rec_nd, sizeof(double) * rec_nd.size()));
-      HIP_OK(hipMemcpyAsync(d_rec_nd, rec_nd.data(), sizeof(double) * rec_nd.size(), hipMemcpyHostToDevice, t->stream));
-    }
-    HIP_OK(hipMemcpyAsync(d_idx, sort_sum.data(), sizeof(int) * (size_t)n_all, hipMemcpyHostToDevice, t->stream));
-    HIP_OK(hipMemsetAsync(t->d_flag, 0, sizeof(int), t->stream));
-    HIP_OK(hipMemsetAsync(t->d_nn, 0xff, sizeof(int) * (size_t)n_all * t->m, t->stream));
-    gpb::NNKernelArgs na;
-    na.sorted_rec = d_rec; na.sorted_idx = d_idx; na.pts = t->d_pts; na.nn = t->d_nn; na.has_duplicates = t->d_flag; na.n = n_all; na.m = t->m;
-    na.sorted_nd = d_rec_nd; na.coords_nd = t->d_coords_nd;
-    const int start_at = all_rows ? 0 : n_obs;
-    na.start_at = start_at; na.end_search_at = cond_all ? n_all - 2 : n_obs - 1; na.pos0 = 0; na.pos1 = n_all;
-    // only the appended rows are searched (all_rows: every row): their positions, grouped like the training-time search
-    std::vector<int> qorder((size_t)std::max(all_rows ? n_all : n_pred, 1));
-    int nq = 0;
-    gpb::nn_query_order(sort_sum.data(), 0, n_all, t->m, start_at, qorder.data(), &nq);
-    HIP_OK(hipMalloc(&d_qorder, sizeof(int) * qorder.size()));
-    HIP_OK(hipMemcpyAsync(d_qorder, qorder.data(), sizeof(int) * (size_t)std::max(nq, 1), hipMemcpyHostToDevice, t->stream));
-    na.qorder = d_qorder; na.nq = nq;
-    HIP_OK(gpb::launch_vecchia_nn(d, na, t->stream));
-    int flag = 0;
-    HIP_OK(hipMemcpyAsync(&flag, t->d_flag, sizeof(int), hipMemcpyDeviceToHost, t->stream));
-    HIP_OK(hipStreamSynchronize(t->stream));
-    if (has_duplicates) *has_duplicates = flag;
-    t->has_nn = true;
-  }
-  t->i_begin = all_rows ? 0 : n_obs; t->i_end = n_all;
-  if (!do_factor) { *out_m = m; return 0; }              // (full-scale Vecchia: the caller runs the residual-process factor)
-  if (gpb_hip_vecchia_factor(t, cov_type, var, a, gauss_likelihood)) return -1;     // non-Gaussian: no nugget, diagonal x (1 + 1e-10) (Vecchia_utils.cpp:1963-1965)
+  // neighbour search for the appended rows only (all_rows: every row); the rows that are not searched stay -1
+  NNSearch q; q.start_at = o.all_rows ? 0 : n_obs; q.end_search_at = o.cond_all ? n_all - 2 : n_obs - 1; q.pos1 = n_all; q.prefill = 0xff;
+  if (search_neighbors(t, call.data(), q, has_duplicates)) return -1;
+  t->has_nn = true; t->i_begin = q.start_at; t->i_end = n_all;
   *out_m = m;
+  return o.factor && gpb_hip_vecchia_factor(t, cov_type, var, a, o.latent ? 0 : 1) ? -1 : 0;
+}
+
+// Rows [row0, row0 + rows) of the neighbour table, A, D and u of a prediction's temporary state to host pointers; a null pointer is not wanted.
+// async: enqueued on the state's stream (the caller synchronises); else synchronous copies.
+static int copy_factor_rows(const gpb_hip_vecchia_t* t, size_t row0, size_t rows, bool async, int32_t* nn, double* A, double* D, double* u) {
+  const size_t m = (size_t)t->m;
+  const auto get = [&](void* dst, const void* src, size_t b) { return async ? hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, t->stream) : hipMemcpy(dst, src, b, hipMemcpyDeviceToHost); };
+  if (nn) HIP_OK(get(nn, t->d_nn + row0 * m, sizeof(int) * rows * m));
+  if (A) HIP_OK(get(A, t->d_A + row0 * m, sizeof(double) * rows * m));
+  if (D) HIP_OK(get(D, t->d_D + row0, sizeof(double) * rows));
+  if (u) HIP_OK(get(u, t->d_u + row0, sizeof(double) * rows));
   return 0;
 }
 
+// The body of the plain prediction entries: search, factor, and the factored rows (the appended ones, or all of them) to the pointers that are wanted.
+static int predict_rows(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred, const PredictOpts& o, int cov_type,
+                        double var, double a, int32_t* m_used, int32_t* nn, double* A, double* D, double* u, int* has_duplicates) {
+  TempVecchia t; int m = 0;
+  if (predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, &t, &m, has_duplicates)) return -1;
+  if (m_used) *m_used = m;
+  const size_t row0 = o.all_rows ? 0 : (size_t)h->n;
+  return copy_factor_rows(t.get(), row0, (size_t)h->n + n_pred - row0, false, nn, A, D, u);
+}
+
+// 'order_obs_first_cond_obs_only', Gaussian likelihood (CondObsOnly = true): pred_mean = -u_p, pred_D = D_p
 int gpb_hip_vecchia_predict_obs_only(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred,
                                      int cov_type, double var, double a, double* pred_mean, double* pred_D, int* has_duplicates) {
   API_BEGIN();
   if (!pred_mean || !pred_D) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, false, cov_type, var, a, &t, &m, has_duplicates);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  const int n_obs = h->n;
-  std::vector<double> u(n_pred);
-  HIP_OK(hipMemcpy(u.data(), t->d_u + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
-  for (int k = 0; k < n_pred; ++k) pred_mean[k] = -u[k];
-  HIP_OK(hipMemcpy(pred_D, t->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
+  if (predict_rows(h, n_pred, coords_pred_colmajor, num_neighbors_pred, PredictOpts(), cov_type, var, a, nullptr, nullptr, nullptr, pred_D, pred_mean, has_duplicates)) return -1;
+  for (int k = 0; k < n_pred; ++k) pred_mean[k] = -pred_mean[k];
   API_END();
 }
 
@@ -1853,36 +1834,23 @@ int gpb_hip_vecchia_predict_latent_obs_only(gpb_hip_vecchia_t* h, int32_t n_pred
                                             int cov_type, double var, double a, double* pred_mean, int* has_duplicates) {
   API_BEGIN();
   if (!pred_mean) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, false, cov_type, var, a, &t, &m, has_duplicates, 0);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  std::vector<double> u(n_pred);
-  HIP_OK(hipMemcpy(u.data(), t->d_u + h->n, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
-  for (int k = 0; k < n_pred; ++k) pred_mean[k] = -u[k];
+  PredictOpts o; o.latent = true;
+  if (predict_rows(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, nullptr, nullptr, nullptr, nullptr, pred_mean, has_duplicates)) return -1;
+  for (int k = 0; k < n_pred; ++k) pred_mean[k] = -pred_mean[k];
   API_END();
 }
 
-// 'order_obs_first_cond_all' (CondObsOnly = false, Vecchia_utils.cpp:1806-1822, 1883-1975): the factor rows of the appended prediction
-// points, which condition on observed AND preceding prediction points.  Outputs, row-major [n_pred][*m_used]: neighbour indices into
-// (observed, prediction) (-1 padded), A_p = C_nn^-1 c, and D_p (nugget included, transformed scale).  The forward substitution with
-// Bp = I - A_pp and the rows of Bp^-1 are the host half (GPB_HIP_PredictCondAllHost).
+// 'order_obs_first_cond_all' (CondObsOnly = false, Vecchia_utils.cpp:1806-1822, 1883-1975): the factor rows of the appended prediction points, which
+// condition on observed AND preceding prediction points.  Outputs, row-major [n_pred][*m_used]: neighbour indices into (observed, prediction) (-1 padded),
+// A_p = C_nn^-1 c, and D_p (nugget included, transformed scale).  The forward substitution with Bp = I - A_pp and the rows of Bp^-1 are the host half
+// (GPB_HIP_PredictCondAllHost).
 int gpb_hip_vecchia_predict_cond_all(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred,
                                      int cov_type, double var, double a, int32_t* m_used, int32_t* nn_pred, double* A_pred, double* D_pred,
                                      int* has_duplicates) {
   API_BEGIN();
   if (!m_used || !nn_pred || !A_pred || !D_pred) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, true, cov_type, var, a, &t, &m, has_duplicates);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  const int n_obs = h->n;
-  *m_used = m;
-  HIP_OK(hipMemcpy(nn_pred, t->d_nn + (size_t)n_obs * m, sizeof(int) * (size_t)n_pred * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(A_pred, t->d_A + (size_t)n_obs * m, sizeof(double) * (size_t)n_pred * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(D_pred, t->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
+  PredictOpts o; o.cond_all = true;
+  if (predict_rows(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, m_used, nn_pred, A_pred, D_pred, nullptr, has_duplicates)) return -1;
   API_END();
 }
 
@@ -1893,16 +1861,8 @@ int gpb_hip_vecchia_predict_cond_all_latent(gpb_hip_vecchia_t* h, int32_t n_pred
                                             int* has_duplicates) {
   API_BEGIN();
   if (!m_used || !nn_pred || !A_pred || !D_pred) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, true, cov_type, var, a, &t, &m, has_duplicates, 0);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  const int n_obs = h->n;
-  *m_used = m;
-  HIP_OK(hipMemcpy(nn_pred, t->d_nn + (size_t)n_obs * m, sizeof(int) * (size_t)n_pred * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(A_pred, t->d_A + (size_t)n_obs * m, sizeof(double) * (size_t)n_pred * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(D_pred, t->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
+  PredictOpts o; o.cond_all = true; o.latent = true;
+  if (predict_rows(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, m_used, nn_pred, A_pred, D_pred, nullptr, has_duplicates)) return -1;
   API_END();
 }
 
@@ -1912,10 +1872,26 @@ int gpb_hip_vecchia_predict_cond_all_latent(gpb_hip_vecchia_t* h, int32_t n_pred
 // RESIDUAL-process factor rows (A_p, D_p, u_p = -A_p y_nn) and (B C)_p = C_p - A_p C_nn for the appended rows.  The caller combines them with the
 // Woodbury quantities of the observed points (GPB_PredictREModel): mean = -u_p + (B C)_p W^-1 (B C)' D^-1 B y, var = D_p + (B C)_p W^-1 (B C)_p'.
 // ip_colmajor: k x d inducing points; Linv_rowmajor: inverse Cholesky factor of Sigma_m (as gpb_hip_vecchia_vif_factor takes it).
-// Outputs: u_pred, D_pred (n_pred), BC_pred (n_pred x k, row-major).
+// Outputs: u_pred, D_pred (n_pred), BC_pred (n_pred x k, row-major); with nn_pred also *m_used and the rows nn_pred, A_pred of [Bpo Bp].
 static int vif_predict_appended(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred, bool cond_all,
                                 const double* ip_colmajor, int cov_type, double var, double a, const double* Linv_rowmajor,
-                                double* u_pred, double* D_pred, double* BC_pred, int* has_duplicates, int32_t* m_used, int32_t* nn_pred, double* A_pred);
+                                double* u_pred, double* D_pred, double* BC_pred, int* has_duplicates, int32_t* m_used, int32_t* nn_pred, double* A_pred) {
+  if (!h || !ip_colmajor || !Linv_rowmajor || !u_pred || !D_pred || !BC_pred) return fail("null argument");
+  if (h->vif_k < 1) return fail("no inducing points have been set (call gpb_hip_vecchia_vif_set_inducing_points)");
+  TempVecchia tp; int m = 0;
+  PredictOpts o; o.cond_all = cond_all; o.factor = false;
+  if (predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, &tp, &m, has_duplicates)) return -1;
+  gpb_hip_vecchia_t* t = tp.get();
+  const int n_obs = h->n, n_all = n_obs + n_pred, k = h->vif_k, kq = h->vif_kq;      // (t gets the same k, so the same padded kq)
+  if (gpb_hip_vecchia_vif_set_inducing_points(t, k, ip_colmajor) || vif_resid_factor(t, n_obs, Linv_rowmajor, cov_type, var, a, false, nullptr)) return -1;
+  HIP_OK(gpb::launch_vif_spmm(t->d_A, t->d_nn, n_obs, n_all, t->m, kq, t->d_vC, t->d_vQ, nullptr, nullptr, t->stream));
+  if (nn_pred) *m_used = m;
+  if (copy_factor_rows(t, n_obs, n_pred, true, nn_pred, A_pred, D_pred, u_pred)) return -1;
+  HIP_OK(hipMemcpy2DAsync(BC_pred, sizeof(double) * (size_t)k, t->d_vQ + (size_t)n_obs * kq, sizeof(double) * (size_t)kq, sizeof(double) * (size_t)k, (size_t)n_pred,
+                          hipMemcpyDeviceToHost, t->stream));
+  HIP_OK(hipStreamSynchronize(t->stream));
+  return 0;
+}
 
 int gpb_hip_vecchia_vif_predict_obs_only(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred,
                                          const double* ip_colmajor, int cov_type, double var, double a, const double* Linv_rowmajor,
@@ -1940,50 +1916,6 @@ int gpb_hip_vecchia_vif_predict_cond_all(gpb_hip_vecchia_t* h, int32_t n_pred, c
   API_END();
 }
 
-static int vif_predict_appended(gpb_hip_vecchia_t* h, int32_t n_pred, const double* coords_pred_colmajor, int32_t num_neighbors_pred, bool cond_all,
-                                const double* ip_colmajor, int cov_type, double var, double a, const double* Linv_rowmajor,
-                                double* u_pred, double* D_pred, double* BC_pred, int* has_duplicates, int32_t* m_used, int32_t* nn_pred, double* A_pred) {
-  {
-  if (!h || !ip_colmajor || !Linv_rowmajor || !u_pred || !D_pred || !BC_pred) return fail("null argument");
-  if (h->vif_k < 1) return fail("no inducing points have been set (call gpb_hip_vecchia_vif_set_inducing_points)");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, cond_all, cov_type, var, a, &t, &m, has_duplicates, 1, false, false, false);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  const int n_obs = h->n, n_all = n_obs + n_pred, k = h->vif_k;
-  if (gpb_hip_vecchia_vif_set_inducing_points(t, k, ip_colmajor)) return -1;
-  const int kp = t->vif_kp, kq = t->vif_kq;
-  if (!t->d_A) {
-    HIP_OK(hipMalloc(&t->d_A, sizeof(double) * (size_t)n_all * t->m));
-    HIP_OK(hipMalloc(&t->d_D, sizeof(double) * (size_t)n_all));
-    HIP_OK(hipMalloc(&t->d_u, sizeof(double) * (size_t)n_all));
-  }
-  if (vif_upload_matrix(t, 0, Linv_rowmajor, true)) return -1;
-  HIP_OK(gpb::launch_vif_crosscov(cov_type, t->d_pts, t->d_ip, 0, n_all, k, kq, t->d, var, a, t->d_vC, nullptr, t->stream));
-  HIP_OK(gpb::launch_vif_gemm(t->d_vC, t->d_vM, n_all, kq, t->d_V, false, t->stream));
-  gpb::VecchiaKernelArgs ka;
-  ka.pts = t->d_pts; ka.nn = t->d_nn; ka.exp_tab = t->d_exp_tab; ka.partials = t->d_vif_part;
-  ka.A = t->d_A; ka.D = t->d_D; ka.u = t->d_u;
-  ka.m = t->m; ka.i_begin = n_obs; ka.i_end = n_all;
-  ka.var = var; ka.a = a; ka.diag_nn = var + 1.0; ka.diag_i = var + 1.0; ka.nugget = 1.0;
-  HIP_OK(gpb::launch_vif_resid_factor(cov_type, ka, t->d_V, k, kq, t->stream));
-  // (B C) of the appended rows
-  HIP_OK(gpb::launch_vif_spmm(t->d_A, t->d_nn, n_obs, n_all, t->m, kq, t->d_vC, t->d_vQ, nullptr, nullptr, t->stream));
-  HIP_OK(hipMemcpyAsync(u_pred, t->d_u + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost, t->stream));
-  HIP_OK(hipMemcpyAsync(D_pred, t->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost, t->stream));
-  HIP_OK(hipMemcpy2DAsync(BC_pred, sizeof(double) * (size_t)k, t->d_vQ + (size_t)n_obs * kq, sizeof(double) * (size_t)kq, sizeof(double) * (size_t)k, (size_t)n_pred,
-                          hipMemcpyDeviceToHost, t->stream));
-  if (nn_pred) {
-    *m_used = m;
-    HIP_OK(hipMemcpyAsync(nn_pred, t->d_nn + (size_t)n_obs * m, sizeof(int) * (size_t)n_pred * m, hipMemcpyDeviceToHost, t->stream));
-    HIP_OK(hipMemcpyAsync(A_pred, t->d_A + (size_t)n_obs * m, sizeof(double) * (size_t)n_pred * m, hipMemcpyDeviceToHost, t->stream));
-  }
-  HIP_OK(hipStreamSynchronize(t->stream));
-  }
-  return 0;
-}
-
 // Factor rows of EVERY point of a joint (observed, prediction) ordering -- the device half of the prediction types that re-factor the
 // observed points too:
 //   layout 1, 'order_pred_first' (CalcPredVecchiaPredictedFirstOrder, Vecchia_utils.cpp:2228-2255, 2328-2416): prediction points first,
@@ -1997,68 +1929,8 @@ int gpb_hip_vecchia_predict_joint_factor(gpb_hip_vecchia_t* h, int32_t n_pred, c
                                          int32_t* m_used, int32_t* nn_all, double* A_all, double* D_all, double* u_all, int* has_duplicates) {
   API_BEGIN();
   if (!m_used || !nn_all || !A_all || !D_all) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, cond_all != 0, cov_type, var, a, &t, &m, has_duplicates,
-                                         gauss_likelihood, layout_pred_first != 0, true);
-  struct Guard { gpb_hip_vecchia_t* p; ~Guard() { if (p) gpb_hip_vecchia_free(p); } } guard{t};
-  if (rc) return -1;
-  const size_t n_all = (size_t)h->n + n_pred;
-  *m_used = m;
-  HIP_OK(hipMemcpy(nn_all, t->d_nn, sizeof(int) * n_all * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(A_all, t->d_A, sizeof(double) * n_all * m, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(D_all, t->d_D, sizeof(double) * n_all, hipMemcpyDeviceToHost));
-  if (u_all) HIP_OK(hipMemcpy(u_all, t->d_u, sizeof(double) * n_all, hipMemcpyDeviceToHost));
-  API_END();
-}
-
-// Dense symmetric positive definite service for the prediction types above (the conditional precision matrices the reference hands to
-// its sparse Cholesky, Vecchia_utils.cpp:2419-2441, 2601-2650): x = M^-1 rhs and / or rows and columns [sub0, n) of M^-1, by the exact-GP
-// machinery -- the blocked MFMA Cholesky (dense_kernels.hip); the inverse as the Schur complement of ONE partial factorisation of
-// [[M, .], [I, 0]] (-M^-1 in the bottom-right block, as gpb_hip_exact_grad_terms).  M_host: row-major n x n, lower triangle significant.
-// inv_sub_host: (n - sub0)^2 row-major, symmetric.  n <= 24000 with the inverse, <= 60000 without.
-int gpb_hip_dense_spd_solve(int32_t n, const double* M_host, const double* rhs_host, double* x_host, int32_t sub0, double* inv_sub_host) {
-  API_BEGIN();
-  if (!M_host || n < 1 || (!x_host && !inv_sub_host) || (x_host && !rhs_host)) return fail("gpb_hip_dense_spd_solve: invalid argument");
-  if (check_device()) return -1;
-  const bool inv = inv_sub_host != nullptr;
-  if (inv && (sub0 < 0 || sub0 >= n)) return fail("gpb_hip_dense_spd_solve: sub0 = %d", sub0);
-  if (n > (inv ? 24000 : 60000)) return fail("gpb_hip_dense_spd_solve: n = %d is too large for the dense path (%s)", n, inv ? "inverse: 24000" : "solve: 60000");
-  const int np = ((n + 63) / 64) * 64, ld = inv ? 2 * np : np;
-  struct Bufs {
-    double *P = nullptr, *y = nullptr, *z = nullptr, *x = nullptr, *work = nullptr, *out = nullptr; int* info = nullptr; hipStream_t st = nullptr;
-    ~Bufs() { dev_free(P); dev_free(y); dev_free(z); dev_free(x); dev_free(work); dev_free(out); dev_free(info); if (st) (void)hipStreamDestroy(st); }
-  } b;
-  HIP_OK(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
-  HIP_OK(hipMalloc(&b.P, sizeof(double) * (size_t)ld * ld));
-  HIP_OK(hipMalloc(&b.y, sizeof(double) * (size_t)np)); HIP_OK(hipMalloc(&b.z, sizeof(double) * (size_t)np));
-  HIP_OK(hipMalloc(&b.x, sizeof(double) * (size_t)np)); HIP_OK(hipMalloc(&b.work, sizeof(double) * (size_t)np));
-  HIP_OK(hipMalloc(&b.out, sizeof(double) * 2)); HIP_OK(hipMalloc(&b.info, sizeof(int)));
-  HIP_OK(hipMemsetAsync(b.P, 0, sizeof(double) * (size_t)ld * ld, b.st));
-  HIP_OK(hipMemsetAsync(b.info, 0, sizeof(int), b.st));
-  HIP_OK(hipMemsetAsync(b.y, 0, sizeof(double) * (size_t)np, b.st));
-  HIP_OK(hipMemcpy2DAsync(b.P, sizeof(double) * (size_t)ld, M_host, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice, b.st));
-  if (np > n) {                                    // identity on the padding: the factor of the padded matrix is that of M
-    std::vector<double> ones((size_t)(np - n), 1.0);
-    HIP_OK(hipMemcpy2DAsync(b.P + (size_t)n * ld + n, sizeof(double) * ((size_t)ld + 1), ones.data(), sizeof(double), sizeof(double), (size_t)(np - n),
-                            hipMemcpyHostToDevice, b.st));
-    HIP_OK(hipStreamSynchronize(b.st));
-  }
-  if (rhs_host) HIP_OK(hipMemcpyAsync(b.y, rhs_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, b.st));
-  if (inv) HIP_OK(gpb::launch_dense_aug_identity(b.P, np, ld, b.st));
-  HIP_OK(gpb::launch_dense_cholesky(b.P, ld, b.info, b.st, nullptr, nullptr, nullptr, np));
-  if (x_host) HIP_OK(gpb::launch_dense_solve(b.P, n, np, ld, b.y, b.z, b.out, b.x, b.st, b.work));
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(&info, b.info, sizeof(int), hipMemcpyDeviceToHost, b.st));
-  if (x_host) HIP_OK(hipMemcpyAsync(x_host, b.x, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, b.st));
-  const int ns = n - sub0;
-  if (inv) HIP_OK(hipMemcpy2DAsync(inv_sub_host, sizeof(double) * (size_t)ns, b.P + (size_t)(np + sub0) * ld + np + sub0, sizeof(double) * (size_t)ld,
-                                   sizeof(double) * (size_t)ns, (size_t)ns, hipMemcpyDeviceToHost, b.st));
-  HIP_OK(hipStreamSynchronize(b.st));
-  if (info != 0) return fail("the conditional precision matrix is not positive definite (dense Cholesky failed)");
-  if (inv) for (int i = 0; i < ns; ++i) {          // the Schur complement holds -M^-1 in its lower triangle
-    for (int j = 0; j <= i; ++j) { const double v = -inv_sub_host[(size_t)i * ns + j]; inv_sub_host[(size_t)i * ns + j] = v; inv_sub_host[(size_t)j * ns + i] = v; }
-  }
+  PredictOpts o; o.cond_all = cond_all != 0; o.latent = gauss_likelihood == 0; o.pred_first = layout_pred_first != 0; o.all_rows = true;
+  if (predict_rows(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, m_used, nn_all, A_all, D_all, u_all, has_duplicates)) return -1;
   API_END();
 }
 
@@ -2100,361 +1972,6 @@ int gpb_hip_vecchia_newton_leaf_values(gpb_hip_vecchia_t* h, const int32_t* leaf
   }
   for (int i = 0; i < L; ++i) { double t = rhs[i]; for (int k = 0; k < i; ++k) t -= G[(size_t)i * L + k] * leaf_values[k]; leaf_values[i] = t / G[(size_t)i * L + i]; }
   for (int i = L - 1; i >= 0; --i) { double t = leaf_values[i]; for (int k = i + 1; k < L; ++k) t -= G[(size_t)k * L + i] * leaf_values[k]; leaf_values[i] = t / G[(size_t)i * L + i]; }
-  API_END();
-}
-
-// The stream of the look-ahead ("REST") updates of the blocked Cholesky (dense_kernels.hip: launch_dense_cholesky).
-// Round 6, measured and NOT adopted (profiles/r06_f_dense_cholesky_cu_mask_not_adopted.log): creating it with a CU mask (hipExtStreamCreateWithCUMask) that leaves 16 compute
-// units to the panel chain on the main stream -- a REST update is one 128 x 128 tile per workgroup with 139 KB of LDS, ~55 us each, so its grid occupies every CU and the ~24 small
-// launches of a block column's panel chain queue behind it -- made the n = 16 384 factorisation SLOWER, 65.0 against 43.9 ms (masks of 32 / 64 CUs were not honoured: 43.9 ms).
-static hipError_t create_lookahead_stream(hipStream_t* out) { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }
-
-// Test entry (tests/test_zz_dense_kernels_gpu.py): what launch_dense_cholesky leaves behind.  The row-major ld x ld matrix goes to the device as it is
-// (both triangles), the first ncols columns are factorised -- with the second stream and the two events of the look-ahead when lookahead != 0, with null
-// pointers otherwise -- and the whole array comes back: L in the lower triangle of the first ncols columns, the Schur complement in the lower triangle of
-// the rest, the strict upper triangle as uploaded.  *info is the device's failure word; info != 0 is NOT an error of this call.
-int gpb_hip_dense_cholesky_check(int32_t ld, int32_t ncols, int32_t lookahead, const double* M_host, double* out_host, int32_t* info) {
-  API_BEGIN();
-  if (!M_host || !out_host || !info) return fail("gpb_hip_dense_cholesky_check: null argument");
-  if (ld < 64 || ld % 64 != 0 || ld > 24000 || ncols < 1 || ncols > ld) return fail("gpb_hip_dense_cholesky_check: ld = %d (a multiple of 64, <= 24000), ncols = %d (1..ld)", ld, ncols);
-  if (check_device()) return -1;
-  struct Bufs {
-    double* P = nullptr; int* info = nullptr; hipStream_t st = nullptr, st2 = nullptr; hipEvent_t ev_panels = nullptr, ev_rest = nullptr;
-    ~Bufs() {
-      dev_free(P); dev_free(info);
-      if (ev_panels) (void)hipEventDestroy(ev_panels);
-      if (ev_rest) (void)hipEventDestroy(ev_rest);
-      if (st2) (void)hipStreamDestroy(st2);
-      if (st) (void)hipStreamDestroy(st);
-    }
-  } b;
-  const size_t bytes = sizeof(double) * (size_t)ld * ld;
-  HIP_OK(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking));
-  if (lookahead) {
-    HIP_OK(create_lookahead_stream(&b.st2));
-    HIP_OK(hipEventCreateWithFlags(&b.ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&b.ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(hipMalloc(&b.P, bytes));
-  HIP_OK(hipMalloc(&b.info, sizeof(int)));
-  HIP_OK(hipMemsetAsync(b.info, 0, sizeof(int), b.st));
-  HIP_OK(hipMemcpyAsync(b.P, M_host, bytes, hipMemcpyHostToDevice, b.st));
-  HIP_OK(gpb::launch_dense_cholesky(b.P, ld, b.info, b.st, b.st2, b.ev_panels, b.ev_rest, ncols));
-  int dev_info = 0;
-  HIP_OK(hipMemcpyAsync(&dev_info, b.info, sizeof(int), hipMemcpyDeviceToHost, b.st));
-  HIP_OK(hipMemcpyAsync(out_host, b.P, bytes, hipMemcpyDeviceToHost, b.st));
-  HIP_OK(hipStreamSynchronize(b.st));
-  if (b.st2) HIP_OK(hipStreamSynchronize(b.st2));
-  *info = dev_info;
-  API_END();
-}
-
-// ------------------------------------------------------------------------------------------
-int gpb_hip_exact_create(int32_t n, int32_t d, const double* coords_colmajor, gpb_hip_exact_t** out) {
-  API_BEGIN();
-  if (!out) return fail("gpb_hip_exact_create: out is NULL");
-  *out = nullptr;
-  if (check_device()) return -1;
-  if (n < 1 || d < 1 || d > 3 || !coords_colmajor) return fail("gpb_hip_exact_create: invalid arguments (n = %d, d = %d; d in 1..3)", n, d);
-  if (n > 100000) return fail("gpb_hip_exact_create: n = %d is too large for the dense path (use gp_approx = 'vecchia')", n);
-  auto* h = new gpb_hip_exact();
-  bool built = false;
-  const auto drop_half_built = scope_exit([&] { if (!built) gpb_hip_exact_free(h); });
-  h->n = n; h->d = d; h->np = ((n + 63) / 64) * 64;
-  HIP_OK(hipGetDevice(&h->device));
-  {   // the main stream carries the panel chain of the factorisation (latency-bound, the critical path); the look-ahead updates run on
-      // stream2 at normal priority
-    int lo = 0, hi = 0;
-    HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIP_OK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, hi));
-  }
-  std::vector<double4> pts(n);
-  for (int i = 0; i < n; ++i) {
-    pts[i].x = coords_colmajor[i];
-    pts[i].y = d > 1 ? coords_colmajor[(size_t)n + i] : 0.0;
-    pts[i].z = d > 2 ? coords_colmajor[(size_t)2 * n + i] : 0.0;
-    pts[i].w = 0.0;
-  }
-  HIP_OK(hipMalloc(&h->d_pts, sizeof(double4) * (size_t)n));
-  HIP_OK(hipMemcpy(h->d_pts, pts.data(), sizeof(double4) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc(&h->d_P, sizeof(double) * (size_t)(h->np + 64) * (h->np + 64)));     // + the 64-row block that carries y (gpb_hip_exact_nll_terms)
-  HIP_OK(hipMalloc(&h->d_y, sizeof(double) * (size_t)h->np));
-  HIP_OK(hipMalloc(&h->d_z, sizeof(double) * (size_t)h->np));
-  HIP_OK(hipMalloc(&h->d_x, sizeof(double) * (size_t)h->np));
-  HIP_OK(hipMalloc(&h->d_work, sizeof(double) * (size_t)h->np));
-  HIP_OK(hipMalloc(&h->d_out, sizeof(double) * 2));
-  HIP_OK(hipMalloc(&h->d_info, sizeof(int)));
-  const std::vector<double> tab = exp_table();
-  HIP_OK(hipMalloc(&h->d_exp_tab, GPB_EXP_TAB_SIZE * sizeof(double)));
-  HIP_OK(hipMemcpy(h->d_exp_tab, tab.data(), GPB_EXP_TAB_SIZE * sizeof(double), hipMemcpyHostToDevice));
-  built = true;
-  *out = h;
-  API_END();
-}
-
-int gpb_hip_exact_free(gpb_hip_exact_t* h) {
-  API_BEGIN();
-  if (!h) return 0;
-  (void)hipSetDevice(h->device);
-  if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-  if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-  if (h->ev_panels) (void)hipEventDestroy(h->ev_panels);
-  if (h->ev_rest) (void)hipEventDestroy(h->ev_rest);
-  dev_free(h->d_pts); dev_free(h->d_P); dev_free(h->d_y); dev_free(h->d_z); dev_free(h->d_x); dev_free(h->d_out); dev_free(h->d_work);
-  dev_free(h->d_exp_tab); dev_free(h->d_info); dev_free(h->d_P2); dev_free(h->d_gpart); dev_free(h->d_g4);
-  delete h;
-  API_END();
-}
-
-int gpb_hip_exact_set_y(gpb_hip_exact_t* h, const double* y_host) {
-  API_BEGIN();
-  if (!h || !y_host) return fail("null argument");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipMemcpyAsync(h->d_y, y_host, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  h->has_y = true;
-  API_END();
-}
-
-int gpb_hip_exact_nll_terms(gpb_hip_exact_t* h, int cov_type, double var, double a, double* out2_host, double* yaux_host,
-                            double* ms3) {
-  API_BEGIN();
-  if (!h || !out2_host) return fail("null argument");
-  if (!h->has_y) return fail("response data has not been set (call gpb_hip_exact_set_y)");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
-  HIP_OK(hipSetDevice(h->device));
-  hipEvent_t e[4];
-  for (auto& ev : e) HIP_OK(hipEventCreate(&ev));
-  HIP_OK(hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-  HIP_OK(hipEventRecord(e[0], h->stream));
-  // Two forms.  yrow (default): y rides along as row np of the (np + 64)-row matrix -- the panel solves of the factorisation leave
-  // z = L^-1 y in that row and the trailing update leaves -z'z at [np][np]: no forward substitution (np / 64 launches less; the backward
-  // one only when y_aux is asked for).  (Round 2's form -- the np x np matrix and both substitutions -- was removed in round 4.)
-  const int ld = h->np + 64;
-  HIP_OK(hipMemsetAsync(h->d_P + (size_t)h->np * ld, 0, sizeof(double) * (size_t)64 * ld, h->stream));
-  HIP_OK(gpb::launch_dense_cov(cov_type, h->d == 3, h->d_pts, h->n, h->np, ld, var, a, 1.0, h->d_exp_tab, h->d_P, h->stream));   // Psi = Sigma + I (:9273-9287)
-  HIP_OK(gpb::launch_dense_set_yrow(h->d_P, h->n, h->np, ld, h->d_y, h->stream));
-  HIP_OK(hipEventRecord(e[1], h->stream));
-  if (!h->stream2) {
-    HIP_OK(create_lookahead_stream(&h->stream2));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(gpb::launch_dense_cholesky(h->d_P, ld, h->d_info, h->stream, h->stream2, h->ev_panels, h->ev_rest, h->np));
-  HIP_OK(hipEventRecord(e[2], h->stream));
-  HIP_OK(gpb::launch_dense_yrow_sums(h->d_P, h->n, h->np, ld, h->d_out, h->stream));
-  if (yaux_host) {
-    HIP_OK(hipMemcpyAsync(h->d_work, h->d_P + (size_t)h->np * ld, sizeof(double) * (size_t)h->np, hipMemcpyDeviceToDevice, h->stream));
-    HIP_OK(gpb::launch_dense_solve_backward(h->d_P, h->np, ld, h->d_work, h->d_x, h->stream));
-  }
-  HIP_OK(hipEventRecord(e[3], h->stream));
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(out2_host, h->d_out, sizeof(double) * 2, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (yaux_host) HIP_OK(hipMemcpyAsync(yaux_host, h->d_x, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (ms3) for (int t = 0; t < 3; ++t) { float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, e[t], e[t + 1])); ms3[t] = ms; }
-  for (auto& ev : e) (void)hipEventDestroy(ev);
-  if (info != 0) return fail("the covariance matrix is not positive definite (dense Cholesky failed)");
-  API_END();
-}
-
-/* Likelihood terms AND the covariance-parameter gradient sums of the exact (dense) GP: CalcGradPars, dense branch
-   (re_model_template.h:2016-2040) with CalcPsiInv (:6586-6614).  Psi^-1 comes out of ONE partial factorisation: the blocked Cholesky run
-   on the first np columns of [[Psi, .], [I, 0]] leaves L in the top-left block, L^-T below it and -L^-T L^-1 = -Psi^-1 as the Schur
-   complement in the bottom-right block (the same MFMA trailing updates as the factorisation itself).  out7 has the layout of
-   gpb_hip_vecchia_grad_terms: {y' Psi^-1 y, log|Psi|, 0, g1_var, g2_var, g1_range, g2_range}, gradient_k = g1_k / sigma2 + g2_k. */
-int gpb_hip_exact_grad_terms(gpb_hip_exact_t* h, int cov_type, double var, double a, double* out7_host) {
-  API_BEGIN();
-  if (!h || !out7_host) return fail("null argument");
-  if (!h->has_y) return fail("response data has not been set (call gpb_hip_exact_set_y)");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
-  if (h->n > 24000) return fail("gpb_hip_exact_grad_terms: n = %d is too large for the dense gradient (the augmented matrix has (2 n)^2 entries); use gp_approx = 'vecchia'", h->n);
-  HIP_OK(hipSetDevice(h->device));
-  const int np = h->np, ld = 2 * np, ntiles = gpb::dense_grad_num_tiles(np);
-  if (!h->d_P2) {
-    HIP_OK(hipMalloc(&h->d_P2, sizeof(double) * (size_t)ld * ld));
-    HIP_OK(hipMalloc(&h->d_gpart, sizeof(double) * 4 * (size_t)ntiles));
-    HIP_OK(hipMalloc(&h->d_g4, sizeof(double) * 8));
-  }
-  if (!h->stream2) {
-    HIP_OK(create_lookahead_stream(&h->stream2));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-  HIP_OK(hipMemsetAsync(h->d_P2, 0, sizeof(double) * (size_t)ld * ld, h->stream));
-  HIP_OK(gpb::launch_dense_cov(cov_type, h->d == 3, h->d_pts, h->n, np, ld, var, a, 1.0, h->d_exp_tab, h->d_P2, h->stream));
-  HIP_OK(gpb::launch_dense_aug_identity(h->d_P2, np, ld, h->stream));
-  HIP_OK(gpb::launch_dense_cholesky(h->d_P2, ld, h->d_info, h->stream, h->stream2, h->ev_panels, h->ev_rest, np));
-  HIP_OK(gpb::launch_dense_solve(h->d_P2, h->n, np, ld, h->d_y, h->d_z, h->d_out, h->d_x, h->stream, h->d_work));           // y' Psi^-1 y, log|Psi|, ya = Psi^-1 y
-  HIP_OK(gpb::launch_dense_grad(cov_type, h->d == 3, h->d_pts, h->n, np, ld, var, a, h->d_exp_tab, h->d_P2, h->d_x, h->d_gpart, h->stream));
-  HIP_OK(gpb::launch_reduce_partials(h->d_gpart, ntiles, 4, h->d_g4, nullptr, h->stream));
-  double o2[2], g4[4];
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(o2, h->d_out, sizeof(double) * 2, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(g4, h->d_g4, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (info != 0) return fail("the covariance matrix is not positive definite (dense Cholesky failed)");
-  // g4 = {S.yy, S.W, dS.yy, dS.W} with W = -Psi^-1:  -1/2 ya' dPsi ya  and  1/2 tr(Psi^-1 dPsi) = -1/2 sum dPsi o W
-  out7_host[0] = o2[0]; out7_host[1] = o2[1]; out7_host[2] = 0.;
-  out7_host[3] = -0.5 * g4[0]; out7_host[4] = -0.5 * g4[1];
-  out7_host[5] = -0.5 * g4[2]; out7_host[6] = -0.5 * g4[3];
-  API_END();
-}
-
-/* diag(Psi^-1) of the exact GP on the transformed scale: the predictive variances of the training-data random effects are sigma2 (1 - diag)
-   (PredictTrainingDataRandomEffects, dense branch: Cov[b | y] = Sigma - Sigma Psi^-1 Sigma = sigma2 (I - Psi_t^-1) with Sigma_t = Psi_t - I).  -Psi^-1 is the
-   Schur complement of the partial factorisation of [[Psi, .], [I, 0]] (as gpb_hip_exact_grad_terms); its diagonal is copied out.  n <= 24000. */
-int gpb_hip_exact_psi_inv_diag(gpb_hip_exact_t* h, int cov_type, double var, double a, double* diag_host) {
-  API_BEGIN();
-  if (!h || !diag_host) return fail("null argument");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
-  if (h->n > 24000) return fail("gpb_hip_exact_psi_inv_diag: n = %d is too large for the dense inverse (the augmented matrix has (2 n)^2 entries)", h->n);
-  HIP_OK(hipSetDevice(h->device));
-  const int np = h->np, ld = 2 * np;
-  if (!h->d_P2) {
-    const int ntiles = gpb::dense_grad_num_tiles(np);
-    HIP_OK(hipMalloc(&h->d_P2, sizeof(double) * (size_t)ld * ld));
-    HIP_OK(hipMalloc(&h->d_gpart, sizeof(double) * 4 * (size_t)ntiles));
-    HIP_OK(hipMalloc(&h->d_g4, sizeof(double) * 8));
-  }
-  if (!h->stream2) {
-    HIP_OK(create_lookahead_stream(&h->stream2));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-  HIP_OK(hipMemsetAsync(h->d_P2, 0, sizeof(double) * (size_t)ld * ld, h->stream));
-  HIP_OK(gpb::launch_dense_cov(cov_type, h->d == 3, h->d_pts, h->n, np, ld, var, a, 1.0, h->d_exp_tab, h->d_P2, h->stream));
-  HIP_OK(gpb::launch_dense_aug_identity(h->d_P2, np, ld, h->stream));
-  HIP_OK(gpb::launch_dense_cholesky(h->d_P2, ld, h->d_info, h->stream, h->stream2, h->ev_panels, h->ev_rest, np));
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpy2DAsync(diag_host, sizeof(double), h->d_P2 + (size_t)np * ld + np, sizeof(double) * ((size_t)ld + 1), sizeof(double), (size_t)h->n,
-                          hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (info != 0) return fail("the covariance matrix is not positive definite (dense Cholesky failed)");
-  for (int i = 0; i < h->n; ++i) diag_host[i] = -diag_host[i];
-  API_END();
-}
-
-/* Prediction of the exact GP at new locations (REModelTemplate::Predict, dense Gaussian branch: mean = Sigma_po Psi^-1 y, covariance =
-   Sigma_pp - Sigma_po Psi^-1 Sigma_op; re_model_template.h:4239-4330 with CalcPred).  Transformed scale (Psi = Sigma / sigma2 + I): ONE
-   partial factorisation (first np columns) of [[Psi, ., .], [C, 0, .], [y', 0, 0]], C = Sigma_po / sigma2, leaves
-     mean_out = C Psi^-1 y  (= -Schur[y row][C columns])      q_out = C Psi^-1 C'  (= -Schur[C rows][C columns], n_pred^2 row-major, may be NULL)
-   The caller adds the prior covariance of the prediction points and the scale sigma2.  n_pred <= 20000. */
-int gpb_hip_exact_predict(gpb_hip_exact_t* h, int cov_type, double var, double a, int32_t n_pred, const double* coords_pred_colmajor,
-                          double* mean_out, double* q_out) {
-  API_BEGIN();
-  if (!h || !coords_pred_colmajor || !mean_out) return fail("null argument");
-  if (!h->has_y) return fail("response data has not been set (call gpb_hip_exact_set_y)");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(var > 0.) || !(a > 0.)) return fail("covariance parameters must be positive (var = %g, range = %g)", var, a);
-  if (n_pred < 1 || n_pred > 20000) return fail("gpb_hip_exact_predict: n_pred = %d (1..20000)", n_pred);
-  HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, np = h->np, npp = ((n_pred + 63) / 64) * 64, ld = np + npp + 64, yrow = np + npp;
-  struct Bufs { double* P = nullptr; double4* pred = nullptr; ~Bufs() { dev_free(P); dev_free(pred); } } b;
-  HIP_OK(hipMalloc(&b.P, sizeof(double) * (size_t)ld * ld));
-  HIP_OK(hipMalloc(&b.pred, sizeof(double4) * (size_t)n_pred));
-  std::vector<double4> pp(n_pred);
-  for (int i = 0; i < n_pred; ++i) {
-    pp[i].x = coords_pred_colmajor[i];
-    pp[i].y = h->d > 1 ? coords_pred_colmajor[(size_t)n_pred + i] : 0.0;
-    pp[i].z = h->d > 2 ? coords_pred_colmajor[(size_t)2 * n_pred + i] : 0.0;
-    pp[i].w = 0.0;
-  }
-  HIP_OK(hipMemcpyAsync(b.pred, pp.data(), sizeof(double4) * (size_t)n_pred, hipMemcpyHostToDevice, h->stream));
-  if (!h->stream2) {
-    HIP_OK(create_lookahead_stream(&h->stream2));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-  HIP_OK(hipMemsetAsync(b.P, 0, sizeof(double) * (size_t)ld * ld, h->stream));
-  HIP_OK(gpb::launch_dense_cov(cov_type, h->d == 3, h->d_pts, n, np, ld, var, a, 1.0, h->d_exp_tab, b.P, h->stream));
-  HIP_OK(gpb::launch_dense_cross_cov(cov_type, h->d == 3, h->d_pts, n, b.pred, n_pred, ld, var, a, h->d_exp_tab, b.P, np, h->stream));
-  HIP_OK(gpb::launch_dense_set_row(b.P, n, ld, yrow, h->d_y, h->stream));
-  HIP_OK(gpb::launch_dense_cholesky(b.P, ld, h->d_info, h->stream, h->stream2, h->ev_panels, h->ev_rest, np));
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(mean_out, b.P + (size_t)yrow * ld + np, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost, h->stream));
-  if (q_out) HIP_OK(hipMemcpy2DAsync(q_out, sizeof(double) * (size_t)n_pred, b.P + (size_t)np * ld + np, sizeof(double) * (size_t)ld,
-                                     sizeof(double) * (size_t)n_pred, (size_t)n_pred, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (info != 0) return fail("the covariance matrix is not positive definite (dense Cholesky failed)");
-  for (int i = 0; i < n_pred; ++i) mean_out[i] = -mean_out[i];
-  if (q_out) for (int i = 0; i < n_pred; ++i)            // the Schur complement holds -C Psi^-1 C' in its lower triangle
-    for (int j = 0; j <= i; ++j) { const double v = -q_out[(size_t)i * n_pred + j]; q_out[(size_t)i * n_pred + j] = v; q_out[(size_t)j * n_pred + i] = v; }
-  API_END();
-}
-
-/* Standard errors of (sigma2, sigma1_2, rho) of the exact GP from the Fisher information on the ORIGINAL scale: CalcStdDevCovPar ->
-   CalcFisherInformation, dense branch with include_error_var, !transf_scale (re_model_template.h:10788-10815, 10066-10127):
-   FI_ab = 1/2 tr(P dPsi_a P dPsi_b), P = (sigma2 Psi)^-1, dPsi = {I, Sigma / sigma1_2, d(Sigma)/d rho}.  All six traces come out of ONE partial
-   factorisation of a 4 np x 4 np augmented matrix (dense_kernels.hip); with E1 = Sigma_t = ratio k, E2 = dSigma_t / dlog(a) on the transformed
-   scale (ratio = sigma1_2 / sigma2, d/d rho = -(1 / rho) d/dlog a) and T_ab the traces over Psi_t = Sigma_t + I:
-     FI_00 = T_00 / (2 s^4)          FI_01 = T_10 / (2 s^4 ratio)         FI_02 = -T_20 / (2 s^2 rho)      (s^2 = sigma2)
-     FI_11 = T_11 / (2 s^4 ratio^2)  FI_12 = -T_21 / (2 s^2 rho ratio)    FI_22 = T_22 / (2 rho^2)
-   se = sqrt(diag(FI^-1)), NaN where FI is not positive definite (as the reference).  n <= 24000 ((4 n)^2 doubles of device memory). */
-int gpb_hip_exact_fisher_std_errors(gpb_hip_exact_t* h, int cov_type, double sigma2, double ratio, double a, double rho, double* se3_host) {
-  API_BEGIN();
-  if (!h || !se3_host) return fail("null argument");
-  if (cov_type < 0 || cov_type > 2) return fail("covariance type %d is not on the HIP hot path (Matern 0.5/1.5/2.5 only)", cov_type);
-  if (!(sigma2 > 0.) || !(ratio > 0.) || !(a > 0.) || !(rho > 0.)) return fail("covariance parameters must be positive");
-  if (h->n > 24000) return fail("gpb_hip_exact_fisher_std_errors: n = %d is too large for the dense Fisher information (the augmented matrix has (4 n)^2 entries); use gp_approx = 'vecchia'", h->n);
-  HIP_OK(hipSetDevice(h->device));
-  const int np = h->np, ld = 4 * np, ntiles = gpb::dense_grad_num_tiles(np);
-  struct Bufs { double *P = nullptr, *part = nullptr, *t6 = nullptr; ~Bufs() { dev_free(P); dev_free(part); dev_free(t6); } } b;
-  HIP_OK(hipMalloc(&b.P, sizeof(double) * (size_t)ld * ld));
-  HIP_OK(hipMalloc(&b.part, sizeof(double) * 6 * (size_t)ntiles));
-  HIP_OK(hipMalloc(&b.t6, sizeof(double) * 8));
-  if (!h->stream2) {
-    HIP_OK(create_lookahead_stream(&h->stream2));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_panels, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&h->ev_rest, hipEventDisableTiming));
-  }
-  HIP_OK(hipMemsetAsync(h->d_info, 0, sizeof(int), h->stream));
-  HIP_OK(hipMemsetAsync(b.P, 0, sizeof(double) * (size_t)ld * ld, h->stream));
-  HIP_OK(gpb::launch_dense_cov(cov_type, h->d == 3, h->d_pts, h->n, np, ld, ratio, a, 1.0, h->d_exp_tab, b.P, h->stream));
-  HIP_OK(gpb::launch_dense_aug_identity(b.P, np, ld, h->stream));
-  HIP_OK(gpb::launch_dense_deriv_blocks(cov_type, h->d == 3, h->d_pts, h->n, ld, ratio, a, h->d_exp_tab, b.P, 2 * np, 3 * np, h->stream));
-  HIP_OK(gpb::launch_dense_cholesky(b.P, ld, h->d_info, h->stream, h->stream2, h->ev_panels, h->ev_rest, np));
-  HIP_OK(gpb::launch_dense_fisher_sums(b.P, h->n, np, ld, b.part, h->stream));
-  HIP_OK(gpb::launch_reduce_partials(b.part, ntiles, 6, b.t6, nullptr, h->stream));
-  double T[6];
-  int info = 0;
-  HIP_OK(hipMemcpyAsync(T, b.t6, sizeof(double) * 6, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(&info, h->d_info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  if (info != 0) return fail("the covariance matrix is not positive definite (dense Cholesky failed)");
-  const double s2 = sigma2, s4 = sigma2 * sigma2;
-  double FI[3][3];
-  FI[0][0] = T[0] / (2. * s4);
-  FI[0][1] = FI[1][0] = T[1] / (2. * s4 * ratio);
-  FI[0][2] = FI[2][0] = -T[2] / (2. * s2 * rho);
-  FI[1][1] = T[3] / (2. * s4 * ratio * ratio);
-  FI[1][2] = FI[2][1] = -T[4] / (2. * s2 * rho * ratio);
-  FI[2][2] = T[5] / (2. * rho * rho);
-  // sqrt(diag(FI^-1)) through the Cholesky factor (Eigen::LLT in the reference); NaN if it fails
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (int j = 0; j < 3; ++j) se3_host[j] = nan;
-  double L[3][3] = {{0}};
-  bool ok = true;
-  for (int i = 0; i < 3 && ok; ++i) for (int j = 0; j <= i; ++j) {
-    double v = FI[i][j];
-    for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-    if (i == j) { if (!(v > 0.)) { ok = false; break; } L[i][i] = std::sqrt(v); } else L[i][j] = v / L[j][j];
-  }
-  if (ok) for (int c = 0; c < 3; ++c) {          // (FI^-1)_cc = || L^-1 e_c ||^2
-    double z[3] = {0., 0., 0.}, ss = 0.;
-    for (int i = c; i < 3; ++i) { double v = (i == c) ? 1. : 0.; for (int k = c; k < i; ++k) v -= L[i][k] * z[k]; z[i] = v / L[i][i]; ss += z[i] * z[i]; }
-    if (std::isfinite(ss) && ss >= 0.) se3_host[c] = std::sqrt(ss);
-  }
   API_END();
 }
 
@@ -3096,5 +2613,6 @@ int gpb_hip_hist_get_slot(gpb_hip_hist_t* h, int32_t slot, double* hist_out) {
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
+#include "gpb_dense.inc"
 #include "gpb_laplace.inc"
 #include "gpb_tree.inc"

@@ -818,14 +818,7 @@ int pc_factor_sigma(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double 
   s->pc_cols = mcol;
   return 0;
 }
-// buffers of the factor (A, D, u = B y); one launch of the point kernel in factor mode -- the response slot of pts is not used on these paths (u is discarded)
-int lap_alloc_factor(gpb_hip_vecchia_t* h) {
-  if (h->d_A) return 0;
-  HIP_OK(hipMalloc(&h->d_A, sizeof(double) * (size_t)h->n * h->m));
-  HIP_OK(hipMalloc(&h->d_D, sizeof(double) * (size_t)h->n));
-  HIP_OK(hipMalloc(&h->d_u, sizeof(double) * (size_t)h->n));
-  return 0;
-}
+// one launch of the point kernel in factor mode -- the response slot of pts is not used on these paths (u is discarded)
 int lap_launch_factor(gpb_hip_vecchia_t* h, int cov_type, double var, double a, int gauss) {
   const bool had_y = h->has_y;
   h->has_y = true;
@@ -960,23 +953,16 @@ int pc_apply(LaplaceState* s, int n, const double* W, const double* X, double* o
 // ---- full-scale Vecchia with a non-Gaussian likelihood: the device half of CalcSigmaComps + CalcCovFactorVecchia + CalcCovFactorFITC_FSA for a LATENT process
 // (re_model_template.h:8151-8200, :9646-9672; Vecchia_utils.cpp:1412-1414, :1461-1500, :1599-1609): cross-covariances C, V = C L_m^-T, the residual process's factor
 // without a nugget (the neighbours' diagonal x (1 + 1e-10) after the low-rank part is taken off), B C, the Woodbury matrix Sigma_m + (B C)' D^-1 (B C) (k x k: host) ----
-int vif_lap_factor(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double var, double a, bool with_grad, hipStream_t st) {
+int vif_lap_factor(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double var, double a, bool with_grad) {
   const int n = h->n, k = h->vif_k, kq = h->vif_kq;
+  const hipStream_t st = h->stream;
   if ((int)h->vif_ip_host.size() != k * 3) return fail("full-scale Vecchia: the inducing points are not on the host");
   std::vector<double>& Sm = s->vif_Sm; std::vector<double>& Li = s->vif_Linv;
   if (ip_cov_factor(h->vif_ip_host, k, cov_type, var, a, &Sm, &Li, &s->vif_logdet_Sm)) return fail("the covariance matrix of the inducing points is not positive definite");
-  if (vif_upload_matrix(h, 0, Li.data(), true)) return -1;                     // V = C Linv'
   const size_t nkb = sizeof(double) * (size_t)n * kq;
   if (with_grad && !h->d_vdC) { HIP_OK(hipMalloc(&h->d_vdC, nkb)); HIP_OK(hipMalloc(&h->d_vQdC, nkb)); }
   h->vif_has_grad_inputs = false; h->vif_has_grad_factor = false; s->vif_grad_inputs = false;
-  HIP_OK(gpb::launch_vif_crosscov(cov_type, h->d_pts, h->d_ip, 0, n, k, kq, h->d, var, a, h->d_vC, with_grad ? h->d_vdC : nullptr, st));
-  HIP_OK(gpb::launch_vif_gemm(h->d_vC, h->d_vM, n, kq, h->d_V, false, st));
-  gpb::VecchiaKernelArgs ka;
-  ka.pts = h->d_pts; ka.nn = h->d_nn; ka.exp_tab = h->d_exp_tab; ka.partials = h->d_vif_part;
-  ka.A = h->d_A; ka.D = h->d_D; ka.u = h->d_u;
-  ka.m = h->m; ka.i_begin = 0; ka.i_end = n;
-  ka.var = var; ka.a = a; ka.diag_nn = var; ka.diag_i = var; ka.nugget = 0.0; ka.diag_mult = 1.0 + 1e-10;
-  HIP_OK(gpb::launch_vif_resid_factor(cov_type, ka, h->d_V, k, kq, st));
+  if (vif_resid_factor(h, 0, Li.data(), cov_type, var, a, true, with_grad ? h->d_vdC : nullptr)) return -1;
   HIP_OK(gpb::launch_reduce_partials(h->d_vif_part, n, 3, h->d_vout, nullptr, st, nullptr));
   HIP_OK(gpb::launch_vif_spmm(h->d_A, h->d_nn, 0, n, h->m, kq, h->d_vC, h->d_vQ, with_grad ? h->d_vdC : nullptr, with_grad ? h->d_vQdC : nullptr, st));
   HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, kq, h->d_vgpart, h->d_vG, st));
@@ -1318,11 +1304,11 @@ struct LapEvalArgs {
 // factor of Sigma^-1 = B^T D^-1 B without nugget (Vecchia_utils.cpp:1599-1609 jitter); full-scale Vecchia: of the residual process, with the low-rank parts
 int lap_eval_factor(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e) {
   hipStream_t st = h->stream;
-  if (lap_alloc_factor(h)) return -1;
+  if (alloc_factor(h)) return -1;
   if (h->vif_k > 0) {       // gp_approx = "full_scale_vecchia": Sigma = V V' + B^-1 D B^-T (FindModePostRandEffCalcMLLFSVA, likelihoods.h:3379-3750)
     if (s->pc_type != 2 && s->pc_type != 4 && s->pc_type != 5) return fail("full-scale Vecchia with a non-Gaussian likelihood: cg_preconditioner_type must be 'fitc' (the reference's default), 'vifdu' or 'none'");
     if (!s->re_ptr.empty()) return fail("full-scale Vecchia with a non-Gaussian likelihood: repeated locations are not on the HIP hot path");
-    return vif_lap_factor(h, s, e.cov_type, e.var, e.a, e.keep && s->pc_type == 2, st);
+    return vif_lap_factor(h, s, e.cov_type, e.var, e.a, e.keep && s->pc_type == 2);
   }
   if (s->pc_type >= 4) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
   if (lap_launch_factor(h, e.cov_type, e.var, e.a, 0)) return -1;
@@ -2382,33 +2368,17 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   for (int i = 0; i < n; ++i) sim_v[i] = sim_s[s->sigma[i]];
   // ---- the appended rows: neighbours among the observed points, the residual process's factor rows (latent), C_p ----
   if (gpb_hip_vecchia_set_y(h, sim_v.data())) return -1;                                              // the "response" of the appended factor rows: u_p = -A_p s_nn
-  gpb_hip_vecchia_t* tp = nullptr;
-  int m = 0;
+  TempVecchia tmp; int m = 0;
   if (cond_all && n_pred > 5000) return fail("full-scale Vecchia prediction, 'latent_order_obs_first_cond_all': %d > 5000 prediction points (dense B_p^-1)", n_pred);
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, cond_all, cov_type, var, a, &tp, &m, has_duplicates, 0, false, false, false);
-  const auto free_tp = scope_exit([&] { if (tp) gpb_hip_vecchia_free(tp); });
-  if (rc) return -1;
-  const int n_obs = n, n_all = n_obs + n_pred;
+  PredictOpts o; o.cond_all = cond_all; o.latent = true; o.factor = false;
+  if (predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, &tmp, &m, has_duplicates)) return -1;
+  gpb_hip_vecchia_t* tp = tmp.get();
+  const int n_obs = n;
   std::vector<double> ipc((size_t)k * h->d);
   for (int j = 0; j < k; ++j) for (int c = 0; c < h->d; ++c) ipc[(size_t)c * k + j] = h->vif_ip_host[(size_t)j * 3 + c];
-  if (gpb_hip_vecchia_vif_set_inducing_points(tp, k, ipc.data())) return -1;
-  if (!tp->d_A) {
-    HIP_OK(hipMalloc(&tp->d_A, sizeof(double) * (size_t)n_all * tp->m));
-    HIP_OK(hipMalloc(&tp->d_D, sizeof(double) * (size_t)n_all));
-    HIP_OK(hipMalloc(&tp->d_u, sizeof(double) * (size_t)n_all));
-  }
-  if (vif_upload_matrix(tp, 0, s->vif_Linv.data(), true)) return -1;
-  HIP_OK(gpb::launch_vif_crosscov(cov_type, tp->d_pts, tp->d_ip, 0, n_all, k, kq, tp->d, var, a, tp->d_vC, nullptr, tp->stream));
-  HIP_OK(gpb::launch_vif_gemm(tp->d_vC, tp->d_vM, n_all, kq, tp->d_V, false, tp->stream));
-  gpb::VecchiaKernelArgs ka;
-  ka.pts = tp->d_pts; ka.nn = tp->d_nn; ka.exp_tab = tp->d_exp_tab; ka.partials = tp->d_vif_part;
-  ka.A = tp->d_A; ka.D = tp->d_D; ka.u = tp->d_u;
-  ka.m = tp->m; ka.i_begin = n_obs; ka.i_end = n_all;
-  ka.var = var; ka.a = a; ka.diag_nn = var; ka.diag_i = var; ka.nugget = 0.0; ka.diag_mult = 1.0 + 1e-10;
-  HIP_OK(gpb::launch_vif_resid_factor(cov_type, ka, tp->d_V, k, kq, tp->stream));
+  if (gpb_hip_vecchia_vif_set_inducing_points(tp, k, ipc.data()) || vif_resid_factor(tp, n_obs, s->vif_Linv.data(), cov_type, var, a, true, nullptr)) return -1;
   std::vector<double> up(n_pred), Dp(n_pred), Cp((size_t)n_pred * k);
-  HIP_OK(hipMemcpyAsync(up.data(), tp->d_u + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost, tp->stream));
-  HIP_OK(hipMemcpyAsync(Dp.data(), tp->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost, tp->stream));
+  if (copy_factor_rows(tp, n_obs, n_pred, true, nullptr, nullptr, Dp.data(), up.data())) return -1;
   HIP_OK(hipMemcpy2DAsync(Cp.data(), sizeof(double) * (size_t)k, tp->d_vC + (size_t)n_obs * kq, sizeof(double) * (size_t)kq, sizeof(double) * (size_t)k, (size_t)n_pred,
                           hipMemcpyDeviceToHost, tp->stream));
   HIP_OK(hipStreamSynchronize(tp->stream));
@@ -2424,8 +2394,7 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   if (cond_all) {
     std::vector<int32_t> nnh((size_t)n_pred * m);
     std::vector<double> Ah((size_t)n_pred * m);
-    HIP_OK(hipMemcpy(nnh.data(), nn_p, sizeof(int) * nnh.size(), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(Ah.data(), A_p, sizeof(double) * Ah.size(), hipMemcpyDeviceToHost));
+    if (copy_factor_rows(tp, n_obs, n_pred, false, nnh.data(), Ah.data(), nullptr, nullptr)) return -1;
     Rm.assign((size_t)n_pred * n_pred, 0.0);
     std::vector<std::vector<std::pair<int, double>>> Crow(n_pred);
     std::vector<double> acc(n_obs, 0.0); std::vector<char> seen(n_obs, 0); std::vector<int> touched;
@@ -2564,19 +2533,17 @@ int gpb_hip_vecchia_laplace_predict(gpb_hip_vecchia_t* h, int32_t n_pred, const 
   API_BEGIN();
   if (h && h->vif_k > 0) return fail("gpb_hip_vecchia_laplace_predict: full-scale Vecchia handles take gpb_hip_vecchia_vif_laplace_predict / the evaluation and gradient entry points; this one restates the plain Vecchia formulas");
   if (!pred_mean) return fail("null argument");
-  gpb_hip_vecchia_t* t = nullptr;
-  int m = 0;
-  const int rc = predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, false, cov_type, var, a, &t, &m, has_duplicates, 0);
-  const auto free_t = scope_exit([&] { if (t) gpb_hip_vecchia_free(t); });
-  if (rc) return -1;
+  TempVecchia t; int m = 0;
+  PredictOpts o; o.latent = true;
+  if (predict_factor_appended(h, n_pred, coords_pred_colmajor, num_neighbors_pred, o, cov_type, var, a, &t, &m, has_duplicates)) return -1;
   const int n_obs = h->n;
   std::vector<double> u(n_pred), Dp(n_pred);
-  HIP_OK(hipMemcpy(u.data(), t->d_u + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
+  if (copy_factor_rows(t.get(), n_obs, n_pred, false, nullptr, nullptr, nullptr, u.data())) return -1;
   for (int k = 0; k < n_pred; ++k) pred_mean[k] = -u[k];
   if (cg_iterations) *cg_iterations = 0;
   if (pred_var || pred_cov) {
     if (t->m != m) return fail("internal: the appended factor has %d columns, %d neighbours were used", t->m, m);
-    HIP_OK(hipMemcpy(Dp.data(), t->d_D + n_obs, sizeof(double) * (size_t)n_pred, hipMemcpyDeviceToHost));
+    if (copy_factor_rows(t.get(), n_obs, n_pred, false, nullptr, nullptr, Dp.data(), nullptr)) return -1;
     HIP_OK(hipStreamSynchronize(t->stream));
     const bool cov = pred_cov != nullptr;
     std::vector<double> q(cov ? (size_t)n_pred * n_pred : (size_t)n_pred);
@@ -2876,7 +2843,7 @@ int gpb_hip_vecchia_fisher_std_errors(gpb_hip_vecchia_t* h, int cov_type, double
   s->grad_state = false; s->gvec_state = false;
   const int n = h->n, m = h->m;
   hipStream_t st = h->stream;
-  if (lap_alloc_factor(h)) return -1;
+  if (alloc_factor(h)) return -1;
   {
     if (lap_launch_factor(h, cov_type, ratio, a, 1)) return -1;
     HIP_OK(hipStreamSynchronize(st));
@@ -2976,7 +2943,7 @@ int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int cov_type, doub
   HIP_OK(hipSetDevice(h->device));
   const int n = h->n, m = h->m;
   if (h->i_begin != 0 || h->i_end != n) return fail("the Vecchia-Laplace path needs the whole factor on one device");
-  if (lap_alloc_factor(h)) return -1;
+  if (alloc_factor(h)) return -1;
   if (lap_launch_factor(h, cov_type, var, a, 0)) return -1;
   h->has_factor = true;
   if (h->lap) h->lap->grad_state = false;

@@ -201,6 +201,35 @@ class VecchiaState(object):
                                                            C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(mu), _p(Dp), C.byref(dup)))
         return mu, Dp, bool(dup.value)
 
+    def _pred_args(self, coords_pred, num_neighbors_pred, cond_all):
+        """Column-major prediction coordinates and the number of table columns the C side will use (Vecchia_utils.cpp:755-758)."""
+        cp = np.asarray(coords_pred, dtype=np.float64)
+        if cp.ndim == 1:
+            cp = cp.reshape(-1, 1)
+        return np.asfortranarray(cp), cp.shape[0], min(int(num_neighbors_pred), self.n + cp.shape[0] - 1 if cond_all else self.n)
+
+    def predict_cond_all(self, coords_pred, num_neighbors_pred, cov_type, var, a):
+        """-> (nn_pred, A_pred, D_pred, has_duplicates): the factor rows of the appended prediction points, each conditioning on the observed
+        AND the preceding prediction points; nn_pred indexes (observed, prediction), -1 padded."""
+        cm, n_pred, m = self._pred_args(coords_pred, num_neighbors_pred, True)
+        nn = np.empty((n_pred, m), dtype=np.int32); A = np.empty((n_pred, m)); D = np.empty(n_pred); dup = C.c_int(0); m_used = C.c_int32(0)
+        _shim_call(_lib().gpb_hip_vecchia_predict_cond_all(self.h, C.c_int(n_pred), _p(cm), C.c_int(int(num_neighbors_pred)), C.c_int(cov_type), C.c_double(var),
+                                                           C.c_double(a), C.byref(m_used), _p(nn, C.c_int32), _p(A), _p(D), C.byref(dup)))
+        assert m_used.value == m, (m_used.value, m)
+        return nn, A, D, bool(dup.value)
+
+    def predict_joint_factor(self, coords_pred, num_neighbors_pred, layout_pred_first, cond_all, gauss, cov_type, var, a):
+        """-> (nn_all, A_all, D_all, u_all, has_duplicates): the factor rows of EVERY point of the joint ordering, (observed, prediction) or --
+        layout_pred_first -- (prediction, observed)."""
+        cm, n_pred, m = self._pred_args(coords_pred, num_neighbors_pred, cond_all)
+        n_all = self.n + n_pred
+        nn = np.empty((n_all, m), dtype=np.int32); A = np.empty((n_all, m)); D = np.empty(n_all); u = np.empty(n_all); dup = C.c_int(0); m_used = C.c_int32(0)
+        _shim_call(_lib().gpb_hip_vecchia_predict_joint_factor(self.h, C.c_int(n_pred), _p(cm), C.c_int(int(num_neighbors_pred)), C.c_int(1 if layout_pred_first else 0),
+                                                               C.c_int(1 if cond_all else 0), C.c_int(1 if gauss else 0), C.c_int(cov_type), C.c_double(var), C.c_double(a),
+                                                               C.byref(m_used), _p(nn, C.c_int32), _p(A), _p(D), _p(u), C.byref(dup)))
+        assert m_used.value == m, (m_used.value, m)
+        return nn, A, D, u, bool(dup.value)
+
     def newton_leaf_values(self, leaf_index, num_leaves):
         """Needs factor(gauss=True) and yaux() for the current y = F - y; leaf_index in Vecchia order."""
         leaf = np.ascontiguousarray(leaf_index, dtype=np.int32)
