@@ -31,6 +31,7 @@
 #include "hist_kernels.h"
 #include "leaf_kernels.h"
 #include "nn_kernels.h"
+#include "tree_predict_kernels.h"
 #include "vecchia_kernels.h"
 #include "vif_kernels.h"
 #include <fcntl.h>
@@ -459,6 +460,16 @@ struct gpb_hip_hist {
   std::vector<int> blk_f0, blk_bin0, blk_bins; int blk_max = 0;   // per rank: first feature (world + 1 entries), first bin, number of bins; the common padded length
   long long* d_rs_send = nullptr; long long* d_rs_recv = nullptr; double* d_xchg = nullptr; double* h_xchg = nullptr;
   std::vector<int> tree_node_is_cat; std::vector<unsigned> tree_node_cat_bits;   // last tree: per node, is the split categorical / the 8 words of its set of bins
+  // tree scoring (gpb_tree.inc, second half): the arrays of the last tree grown (what gpb_hip_hist_grow_tree handed to its caller), the stored trees
+  // (tree_predict_kernels.h) on the host and on the device, an attached second matrix, and the staging of row lists and results
+  struct LastTree { bool valid = false; int num_leaves = 0; std::vector<int> split_feature, default_left, left_child, right_child; std::vector<uint32_t> threshold;
+                    std::vector<double> leaf_value; } last_tree;
+  std::vector<uint32_t> forest_words; std::vector<int> forest_desc;              // desc: 4 ints per tree {first word, num_leaves, stored bytes, 0}
+  uint32_t* d_forest = nullptr; size_t forest_cap_words = 0; int* d_forest_desc = nullptr; int forest_cap_trees = 0;
+  uint8_t* d_pred_rm = nullptr; int n_pred = 0;                                  // gpb_hip_hist_set_pred_bins: [n_pred][fpad]
+  int* d_prows = nullptr; int* h_prows = nullptr; int prows_cap = 0;             // row list (+ multiplicities behind it): pinned host staging and device copy
+  hipEvent_t ev_prows = nullptr; bool prows_pending = false;                     // the staging buffer's last copy (awaited before it is overwritten)
+  double* d_pscore = nullptr; int pscore_cap = 0; int* d_pleaf = nullptr; int pleaf_cap = 0;
 };
 
 // column-major n x d coordinates -> the kernels' records {x0, x1, x2, 0} (the coordinates beyond the third travel in d_coords_nd)
@@ -581,6 +592,13 @@ int gpb_hip_dev_to_host(void* dst_host, const void* src_dev, uint64_t bytes) {
   API_BEGIN();
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost));
+  API_END();
+}
+int gpb_hip_dev_from_host(void* dst_dev, const void* src_host, uint64_t bytes) {
+  API_BEGIN();
+  if (!dst_dev || !src_host) return fail("null argument");
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));
   API_END();
 }
 
@@ -2076,6 +2094,9 @@ int gpb_hip_hist_free(gpb_hip_hist_t* h) {
   if (h->h_xchg) (void)hipHostFree(h->h_xchg);
   if (h->h_cat_bits2) (void)hipHostFree(h->h_cat_bits2);
   h->comm.release(); dev_free(h->d_limbs);
+  dev_free(h->d_forest); dev_free(h->d_forest_desc); dev_free(h->d_pred_rm); dev_free(h->d_prows); dev_free(h->d_pscore); dev_free(h->d_pleaf);
+  if (h->h_prows) (void)hipHostFree(h->h_prows);
+  if (h->ev_prows) (void)hipEventDestroy(h->ev_prows);
   delete h;
   API_END();
 }

@@ -81,7 +81,7 @@ extern "C" int gpb_hip_hist_grow_tree(gpb_hip_hist_t* h, int32_t num_leaves, dou
   std::vector<double> lval(L, 0.);
   std::vector<int> depth(L, 0);                    // Tree::leaf_depth_ (root 0)
   int* const rows_buf[2] = {h->d_rows, h->d_rows2};
-  h->tree_node_info.clear(); h->tree_node_is_cat.clear(); h->tree_node_cat_bits.clear();
+  h->tree_node_info.clear(); h->tree_node_is_cat.clear(); h->tree_node_cat_bits.clear(); h->last_tree.valid = false;
   const bool any_cat = h->any_cat;
   int ncat_nodes = 0;                              // Tree::SplitCategorical numbers the categorical nodes: threshold_in_bin_ = that index (tree.cpp:76-108)
   bool rows_identity = true;                       // until the first split the root's rows are 0..n-1 (no index list)
@@ -310,6 +310,13 @@ extern "C" int gpb_hip_hist_grow_tree(gpb_hip_hist_t* h, int32_t num_leaves, dou
   }
   *out_num_leaves = nleaves;
   for (int k = 0; k < nleaves; ++k) { leaf_value[k] = lval[k]; leaf_count[k] = gcnt[k]; }
+  {       // the tree as handed to the caller, for gpb_hip_hist_forest_keep_last_tree (valid once this call has succeeded)
+    gpb_hip_hist::LastTree& lt = h->last_tree;
+    lt.num_leaves = nleaves;
+    lt.split_feature.assign(split_feature_inner, split_feature_inner + nnodes); lt.threshold.assign(threshold_in_bin, threshold_in_bin + nnodes);
+    lt.default_left.assign(default_left, default_left + nnodes); lt.left_child.assign(left_child, left_child + nnodes);
+    lt.right_child.assign(right_child, right_child + nnodes); lt.leaf_value.assign(lval.begin(), lval.begin() + nleaves);
+  }
   if (data_leaf_index) {
     if (nleaves == 1) {                              // never split: every row of the root is in leaf 0, rows outside a bag in none (-1)
       std::fill(data_leaf_index, data_leaf_index + n, h->root_cnt > 0 ? -1 : 0);
@@ -340,6 +347,7 @@ extern "C" int gpb_hip_hist_grow_tree(gpb_hip_hist_t* h, int32_t num_leaves, dou
   HIP_OK(hipMemcpyAsync(&part_err, h->d_counts + 3, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   if (part_err) { (void)hipMemset(h->d_counts + 3, 0, sizeof(int)); return fail("gpb_hip_hist_grow_tree: a block of the one-pass partition gave up waiting for its peers "); }
+  h->last_tree.valid = true;
   API_END();
 }
 
@@ -362,5 +370,331 @@ extern "C" int gpb_hip_hist_last_tree_cat_nodes(gpb_hip_hist_t* h, int32_t num_n
   if (num_nodes < 0 || (size_t)num_nodes > h->tree_node_is_cat.size()) return fail("gpb_hip_hist_last_tree_cat_nodes: the last tree has %d nodes", (int)h->tree_node_is_cat.size());
   std::copy(h->tree_node_is_cat.begin(), h->tree_node_is_cat.begin() + num_nodes, is_categorical);
   std::copy(h->tree_node_cat_bits.begin(), h->tree_node_cat_bits.begin() + (size_t)num_nodes * 8, cat_bits8);
+  API_END();
+}
+
+// ---- tree scoring: which leaf does a binned row fall into, score += leaf value (tree_predict_kernels.hip) ----------------------------------
+// Stands in for Tree::AddPredictionToScore on binned rows (src/LightGBM/io/tree.cpp:147, :226; Tree::DecisionInner, include/LightGBM/tree.h:349-409) as
+// GBDT::UpdateScore uses it for the out-of-bag rows and the validation sets of every iteration (src/LightGBM/boosting/gbdt.cpp:606-623,
+// score_updater.hpp:93-96, :118-122).  A tree is compiled when it is stored: per node the 256-bit set of STORED bins of its column that go left.
+namespace {
+
+// The rule of the partition kernels (hist_kernels.hip: make_split_rule + goes_left; DenseBin::SplitInner / SplitCategoricalInner, dense_bin.hpp:176-342,
+// single-feature group: min_bin = 1) restated for the host, stored bins 0 .. 255.  The kernels' own code is left as it is.
+void node_go_left_mask(int max_bin, int default_bin, int most_freq_bin, int missing_type, int default_left, uint32_t threshold, const uint32_t* cat_bits8,
+                       uint32_t* mask8) {
+  for (int w = 0; w < 8; ++w) mask8[w] = 0u;
+  const auto set = [&](int bin, bool left) { if (left) mask8[bin >> 5] |= 1u << (bin & 31); };
+  if (cat_bits8) {
+    const int cat_offset = most_freq_bin == 0 ? 1 : 0;
+    const bool default_goes_left = most_freq_bin > 0 && most_freq_bin < 256 && ((cat_bits8[most_freq_bin >> 5] >> (most_freq_bin & 31)) & 1u);   // :316-320
+    set(0, default_goes_left);
+    for (int bin = 1; bin < 256; ++bin) { const int b = bin - 1 + cat_offset; set(bin, ((cat_bits8[b >> 5] >> (b & 31)) & 1u) != 0u); }
+    return;
+  }
+  const bool miss_zero = missing_type == 1, miss_na = missing_type == 2;
+  const bool mfb_zero = miss_zero && default_bin == most_freq_bin;                                   // dense_bin.hpp:268-272
+  const bool mfb_na = miss_na && (max_bin == most_freq_bin + 1 && most_freq_bin > 0);                // :294-298 with min_bin = 1
+  int th = (int)((threshold + 1u) & 0xffu), tz = (1 + default_bin) & 0xff;                           // VAL_T = uint8_t arithmetic (:182-187)
+  if (most_freq_bin == 0) { th = (th - 1) & 0xff; tz = (tz - 1) & 0xff; }
+  const bool default_goes_left = (unsigned)most_freq_bin <= threshold;                               // :196-199
+  const bool missing_goes_left = (miss_zero || miss_na) && default_left;                             // :200-205
+  const bool zero_is_missing = (miss_na && mfb_na) || (miss_zero && mfb_zero);
+  for (int bin = 0; bin < 256; ++bin) {
+    bool left;
+    if (1 < max_bin) {
+      if ((miss_zero && !mfb_zero && bin == tz) || (miss_na && !mfb_na && bin == max_bin)) left = missing_goes_left;
+      else if (bin == 0) left = zero_is_missing ? missing_goes_left : default_goes_left;
+      else left = !(bin > th);
+    } else {
+      if (miss_zero && !mfb_zero && bin == tz) left = missing_goes_left;
+      else if (bin != max_bin) left = zero_is_missing ? missing_goes_left : default_goes_left;
+      else left = (miss_na && !mfb_na) ? missing_goes_left : (max_bin <= th);
+    }
+    set(bin, left);
+  }
+}
+
+// the stored trees on the device: everything not there yet is uploaded (buffers grow by doubling); ends with a synchronisation, so that the scoring calls
+// themselves copy nothing
+int forest_upload(gpb_hip_hist_t* h, int first_new_tree) {
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));                 // no scoring kernel is reading the buffers
+  int from_tree = first_new_tree;
+  if (h->forest_words.size() > h->forest_cap_words || ntrees > h->forest_cap_trees) {
+    const size_t cw = std::max<size_t>(2 * h->forest_words.size(), 1u << 14);
+    const int ct = std::max(2 * ntrees, 64);
+    dev_free(h->d_forest); dev_free(h->d_forest_desc); h->forest_cap_words = 0; h->forest_cap_trees = 0;
+    HIP_OK(hipMalloc(&h->d_forest, sizeof(uint32_t) * cw));
+    HIP_OK(hipMalloc(&h->d_forest_desc, sizeof(int) * 4 * (size_t)ct));
+    h->forest_cap_words = cw; h->forest_cap_trees = ct;
+    from_tree = 0;
+  }
+  if (from_tree < ntrees) {
+    const size_t w0 = (size_t)h->forest_desc[4 * (size_t)from_tree];
+    HIP_OK(hipMemcpy(h->d_forest + w0, h->forest_words.data() + w0, sizeof(uint32_t) * (h->forest_words.size() - w0), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(h->d_forest_desc + 4 * (size_t)from_tree, h->forest_desc.data() + 4 * (size_t)from_tree, sizeof(int) * 4 * (size_t)(ntrees - from_tree),
+                     hipMemcpyHostToDevice));
+  }
+  return 0;
+}
+
+// validate, compile and store one tree given as the arrays of include/LightGBM/tree.h
+int forest_store(gpb_hip_hist_t* h, const char* who, int num_leaves, const int32_t* split_feature_inner, const uint32_t* threshold_in_bin, const int32_t* default_left,
+                 const int32_t* left_child, const int32_t* right_child, const int32_t* node_is_cat, const uint32_t* node_cat_bits8, const double* leaf_value,
+                 double shrinkage, int32_t* tree_id) {
+  if (!h->has_fix || !h->has_split_info)
+    return fail("%s: the feature metas have not been set (gpb_hip_hist_set_fix_info, gpb_hip_hist_set_split_info): the go-left sets of the nodes need them", who);
+  if (num_leaves < 1) return fail("%s: invalid tree: num_leaves = %d", who, num_leaves);
+  if (!leaf_value) return fail("%s: null argument", who);
+  const int nn = num_leaves - 1, F = h->F;
+  if (nn > 0 && (!split_feature_inner || !threshold_in_bin || !default_left || !left_child || !right_child)) return fail("%s: null argument", who);
+  if ((long long)nn * GPB_TP_NODE_WORDS * 4 + (long long)num_leaves * 8 > GPB_TP_CHUNK_BYTES)
+    return fail("%s: a tree of %d leaves does not fit the %d bytes of LDS a chunk of trees may take (at most 439 leaves)", who, num_leaves, GPB_TP_CHUNK_BYTES);
+  // a tree that cannot spin a walk: every child is a leaf (~leaf, leaf < num_leaves) or a LATER node, every node but the root and every leaf is referenced exactly once
+  std::vector<int> node_refs((size_t)nn, 0), leaf_refs((size_t)num_leaves, 0);
+  for (int i = 0; i < nn; ++i) {
+    if (split_feature_inner[i] < 0 || split_feature_inner[i] >= F) return fail("%s: invalid tree: node %d splits column %d of %d", who, i, split_feature_inner[i], F);
+    for (const int c : {left_child[i], right_child[i]}) {
+      if (c < 0) {
+        if (~c >= num_leaves) return fail("%s: invalid tree: node %d points to leaf %d of %d", who, i, ~c, num_leaves);
+        ++leaf_refs[(size_t)~c];
+      } else {
+        if (c <= i || c >= nn) return fail("%s: invalid tree: node %d has the child node %d (children are later nodes, below %d)", who, i, c, nn);
+        ++node_refs[(size_t)c];
+      }
+    }
+    const bool cat_column = h->any_cat && h->h_is_cat[(size_t)split_feature_inner[i]];
+    const bool cat_node = node_is_cat ? node_is_cat[i] != 0 : cat_column;
+    if (cat_node && (!node_is_cat || !node_cat_bits8)) return fail("%s: node %d is a categorical node without a set of bins (node_is_cat / node_cat_bits8)", who, i);
+  }
+  for (int i = 1; i < nn; ++i) if (node_refs[(size_t)i] != 1) return fail("%s: invalid tree: node %d is referenced %d times", who, i, node_refs[(size_t)i]);
+  if (nn > 0) for (int k = 0; k < num_leaves; ++k) if (leaf_refs[(size_t)k] != 1) return fail("%s: invalid tree: leaf %d is referenced %d times", who, k, leaf_refs[(size_t)k]);
+  const int bytes = gpb::tree_predict_tree_bytes(num_leaves);
+  const size_t w0 = h->forest_words.size();
+  if (w0 + (size_t)bytes / 4 > (size_t)0x7fffffff) return fail("%s: the forest is full", who);
+  h->forest_words.resize(w0 + (size_t)bytes / 4, 0u);
+  uint32_t* w = h->forest_words.data() + w0;
+  for (int i = 0; i < nn; ++i) {
+    const int f = split_feature_inner[i];
+    const bool cat_node = node_is_cat && node_is_cat[i] != 0;
+    node_go_left_mask(h->h_bin_offsets[(size_t)f + 1] - h->h_bin_offsets[(size_t)f] - 1, h->h_meta3[3 * (size_t)f + 1], h->h_fix[2 * (size_t)F + f], h->h_meta3[3 * (size_t)f + 2],
+                      default_left[i] ? 1 : 0, threshold_in_bin[i], cat_node ? node_cat_bits8 + 8 * (size_t)i : nullptr, w + (size_t)i * GPB_TP_NODE_WORDS);
+    uint32_t* m = w + (size_t)i * GPB_TP_NODE_WORDS + 8;
+    m[0] = (uint32_t)f; m[1] = (uint32_t)left_child[i]; m[2] = (uint32_t)right_child[i]; m[3] = 0u;
+  }
+  for (int k = 0; k < num_leaves; ++k) {
+    const double v = leaf_value[k] * shrinkage;              // rounded once, here (Tree::Shrinkage, include/LightGBM/tree.h:188)
+    std::memcpy(w + (size_t)nn * GPB_TP_NODE_WORDS + 2 * (size_t)k, &v, sizeof(double));
+  }
+  const int id = (int)(h->forest_desc.size() / 4);
+  const int desc[4] = {(int)w0, num_leaves, bytes, 0};
+  h->forest_desc.insert(h->forest_desc.end(), desc, desc + 4);
+  if (forest_upload(h, id)) { h->forest_words.resize(w0); h->forest_desc.resize(4 * (size_t)id); return -1; }
+  if (tree_id) *tree_id = id;
+  return 0;
+}
+
+// One scoring call.  rows: HOST indices into the matrix `which` (nullptr: all its rows).  Exactly one of d_score (device, all rows of the matrix) / leaf_out_host.
+int tree_predict_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_begin, int tree_end, const int32_t* rows, int cnt, double* d_score,
+                      int32_t* leaf_out_host, int reps = 0, double* ms_avg = nullptr) {
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  if (tree_begin < 0 || tree_end > ntrees || tree_begin >= tree_end)
+    return fail("%s: trees [%d, %d): the forest holds %d (unknown tree id or empty range)", who, tree_begin, tree_end, ntrees);
+  if (which != 0 && which != 1) return fail("%s: which = %d (0: training rows, 1: the attached matrix)", who, which);
+  if (which == 1 && !h->d_pred_rm) return fail("%s: no second matrix is attached (gpb_hip_hist_set_pred_bins)", who);
+  if (h->fpad > GPB_TP_MAX_FPAD) return fail("%s: rows of %d columns are wider than the %d bytes a staged row may take", who, h->F, GPB_TP_MAX_FPAD);
+  const int N = which == 0 ? h->n : h->n_pred;
+  if (!rows) cnt = N;
+  if (cnt < 0) return fail("%s: cnt = %d", who, cnt);
+  if (cnt == 0) return 0;
+  HIP_OK(hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  gpb::TreePredictArgs a;
+  a.bins_rm = which == 0 ? h->d_bins_rm : h->d_pred_rm; a.fpad = h->fpad; a.rows = nullptr; a.mult = nullptr; a.cnt = cnt;
+  a.forest = h->d_forest; a.desc = reinterpret_cast<const int4*>(h->d_forest_desc); a.tree_begin = tree_begin; a.tree_end = tree_end;
+  a.score = d_score; a.leaf_out = nullptr;
+  if (rows) {
+    bool ascending = true;
+    for (int i = 0; i < cnt; ++i) {
+      if (rows[i] < 0 || rows[i] >= N) return fail("%s: row index %d (position %d) outside the matrix of %d rows", who, rows[i], i, N);
+      if (i > 0 && rows[i] <= rows[i - 1]) ascending = false;
+    }
+    if (h->prows_pending) { HIP_OK(hipEventSynchronize(h->ev_prows)); h->prows_pending = false; }      // the staging buffer is free again
+    if (h->prows_cap < 2 * cnt) {
+      HIP_OK(hipStreamSynchronize(st));
+      dev_free(h->d_prows); if (h->h_prows) { (void)hipHostFree(h->h_prows); h->h_prows = nullptr; } h->prows_cap = 0;
+      HIP_OK(hipMalloc(&h->d_prows, sizeof(int) * 2 * (size_t)cnt));
+      HIP_OK(hipHostMalloc(&h->h_prows, sizeof(int) * 2 * (size_t)cnt));
+      h->prows_cap = 2 * cnt;
+    }
+    if (!h->ev_prows) HIP_OK(hipEventCreateWithFlags(&h->ev_prows, hipEventDisableTiming));
+    int m = cnt;
+    bool with_mult = false;
+    if (d_score && !ascending) {
+      // a list that is unsorted or has repeats: AddPredictionToScore adds once per OCCURRENCE (tree.cpp:226); one lane owns a row, so the list is sorted and
+      // run-length encoded and the lane adds the leaf value as many times as the row occurs -- per row the same additions in the same order
+      std::vector<int> sorted(rows, rows + cnt);
+      std::sort(sorted.begin(), sorted.end());
+      m = 0;
+      for (int i = 0; i < cnt; ++i) {
+        if (m > 0 && h->h_prows[m - 1] == sorted[(size_t)i]) { ++h->h_prows[cnt + m - 1]; continue; }
+        h->h_prows[m] = sorted[(size_t)i]; h->h_prows[cnt + m] = 1; ++m;
+      }
+      with_mult = true;
+    } else {
+      std::copy(rows, rows + cnt, h->h_prows);
+    }
+    HIP_OK(hipMemcpyAsync(h->d_prows, h->h_prows, sizeof(int) * (size_t)(with_mult ? 2 * cnt : cnt), hipMemcpyHostToDevice, st));
+    HIP_OK(hipEventRecord(h->ev_prows, st));
+    h->prows_pending = true;
+    a.rows = h->d_prows; a.mult = with_mult ? h->d_prows + cnt : nullptr; a.cnt = m;
+  }
+  int lds = 0, chunk = 0;                                  // the largest chunk of the range, by the rule of tree_predict_kernels.h
+  for (int t = tree_begin; t < tree_end; ++t) {
+    const int b = h->forest_desc[4 * (size_t)t + 2];
+    if (chunk > 0 && chunk + b > GPB_TP_CHUNK_BYTES) chunk = 0;
+    chunk += b; lds = std::max(lds, chunk);
+  }
+  a.lds_tree_bytes = lds;
+  if (leaf_out_host) {
+    if (h->pleaf_cap < cnt) { HIP_OK(hipStreamSynchronize(st)); dev_free(h->d_pleaf); h->pleaf_cap = 0; HIP_OK(hipMalloc(&h->d_pleaf, sizeof(int) * (size_t)cnt)); h->pleaf_cap = cnt; }
+    a.leaf_out = h->d_pleaf;
+  }
+  HIP_OK(gpb::launch_tree_predict(a, st));
+  if (ms_avg) {      // measurement helper: the launch above was the warm-up; `reps` more of the same launch between two events
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    const auto drop = scope_exit([&] { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); });
+    HIP_OK(hipEventRecord(e0, st));
+    for (int rep = 0; rep < reps; ++rep) HIP_OK(gpb::launch_tree_predict(a, st));
+    HIP_OK(hipEventRecord(e1, st));
+    HIP_OK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    *ms_avg = ms / reps;
+  }
+  if (leaf_out_host) {
+    HIP_OK(hipMemcpyAsync(leaf_out_host, h->d_pleaf, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int gpb_hip_hist_node_go_left_mask(int32_t max_bin, int32_t default_bin, int32_t most_freq_bin, int32_t missing_type, int32_t default_left,
+                                              uint32_t threshold, const uint32_t* cat_bits8, uint32_t* mask8_out) {
+  API_BEGIN();
+  if (!mask8_out) return fail("null argument");
+  if (max_bin < 0 || max_bin > 255 || missing_type < 0 || missing_type > 2)
+    return fail("gpb_hip_hist_node_go_left_mask: max_bin %d (0..255), missing type %d (0..2)", max_bin, missing_type);
+  node_go_left_mask(max_bin, default_bin, most_freq_bin, missing_type, default_left ? 1 : 0, threshold, cat_bits8, mask8_out);
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_add_tree(gpb_hip_hist_t* h, int32_t num_leaves, const int32_t* split_feature_inner, const uint32_t* threshold_in_bin,
+                                            const int32_t* default_left, const int32_t* left_child, const int32_t* right_child, const int32_t* node_is_cat,
+                                            const uint32_t* node_cat_bits8, const double* leaf_value, double shrinkage, int32_t* tree_id) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (forest_store(h, "gpb_hip_hist_forest_add_tree", num_leaves, split_feature_inner, threshold_in_bin, default_left, left_child, right_child, node_is_cat,
+                   node_cat_bits8, leaf_value, shrinkage, tree_id)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_keep_last_tree(gpb_hip_hist_t* h, double shrinkage, int32_t* tree_id) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  const gpb_hip_hist::LastTree& lt = h->last_tree;
+  if (!lt.valid) return fail("gpb_hip_hist_forest_keep_last_tree: no tree has been grown on this handle (gpb_hip_hist_grow_tree)");
+  std::vector<int> is_cat(h->tree_node_is_cat.begin(), h->tree_node_is_cat.end());
+  if (forest_store(h, "gpb_hip_hist_forest_keep_last_tree", lt.num_leaves, lt.split_feature.data(), lt.threshold.data(), lt.default_left.data(), lt.left_child.data(),
+                   lt.right_child.data(), is_cat.data(), h->tree_node_cat_bits.data(), lt.leaf_value.data(), shrinkage, tree_id)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_size(gpb_hip_hist_t* h, int32_t* num_trees) {
+  API_BEGIN();
+  if (!h || !num_trees) return fail("null argument");
+  *num_trees = (int32_t)(h->forest_desc.size() / 4);
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_clear(gpb_hip_hist_t* h) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  h->forest_words.clear(); h->forest_desc.clear();
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_set_pred_bins(gpb_hip_hist_t* h, int32_t n_pred, const uint8_t* bins_fm) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  dev_free(h->d_pred_rm); h->n_pred = 0;
+  if (!bins_fm || n_pred <= 0) return 0;
+  uint8_t* d_fm = nullptr;
+  const auto free_tmp = scope_exit([&] { (void)hipFree(d_fm); });
+  HIP_OK(hipMalloc(&d_fm, (size_t)n_pred * h->F));
+  HIP_OK(hipMemcpy(d_fm, bins_fm, (size_t)n_pred * h->F, hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc(&h->d_pred_rm, (size_t)n_pred * h->fpad));
+  HIP_OK(gpb::launch_bins_transpose(d_fm, h->d_pred_rm, n_pred, h->F, h->fpad, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  h->n_pred = n_pred;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_predict_leaf(gpb_hip_hist_t* h, int32_t which, int32_t tree_id, const int32_t* rows, int32_t cnt, int32_t* leaf_out) {
+  API_BEGIN();
+  if (!h || !leaf_out) return fail("null argument");
+  if (tree_predict_impl(h, "gpb_hip_hist_predict_leaf", which, tree_id, tree_id + 1, rows, cnt, nullptr, leaf_out)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_score_dev(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                          double* score_dev) {
+  API_BEGIN();
+  if (!h || !score_dev) return fail("null argument");
+  if (tree_predict_impl(h, "gpb_hip_hist_add_score_dev", which, tree_begin, tree_end, rows, cnt, score_dev, nullptr)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_score_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                            double* score_dev, int32_t reps, double* ms_avg) {
+  API_BEGIN();
+  if (!h || !score_dev || !ms_avg || reps < 1) return fail("invalid argument");
+  if (tree_predict_impl(h, "gpb_hip_hist_add_score_bench", which, tree_begin, tree_end, rows, cnt, score_dev, nullptr, reps, ms_avg)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_score(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt, double* score) {
+  API_BEGIN();
+  if (!h || !score) return fail("null argument");
+  if (which == 1 && !h->d_pred_rm) return fail("gpb_hip_hist_add_score: no second matrix is attached (gpb_hip_hist_set_pred_bins)");
+  if (which != 0 && which != 1) return fail("gpb_hip_hist_add_score: which = %d (0: training rows, 1: the attached matrix)", which);
+  const int N = which == 0 ? h->n : h->n_pred;
+  HIP_OK(hipSetDevice(h->device));
+  if (h->pscore_cap < N) {
+    HIP_OK(hipStreamSynchronize(h->stream));
+    dev_free(h->d_pscore); h->pscore_cap = 0;
+    HIP_OK(hipMalloc(&h->d_pscore, sizeof(double) * (size_t)N)); h->pscore_cap = N;
+  }
+  HIP_OK(hipMemcpyAsync(h->d_pscore, score, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+  if (tree_predict_impl(h, "gpb_hip_hist_add_score", which, tree_begin, tree_end, rows, cnt, h->d_pscore, nullptr)) { (void)hipStreamSynchronize(h->stream); return -1; }
+  HIP_OK(hipMemcpyAsync(score, h->d_pscore, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_sync(gpb_hip_hist_t* h) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
   API_END();
 }

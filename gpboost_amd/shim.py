@@ -387,6 +387,13 @@ class DeviceBuffer(object):
         _shim_call(_lib().gpb_hip_dev_to_host(_p(out), self.p, C.c_uint64(8 * self.n)))
         return out
 
+    def from_host(self, values):
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.size != self.n:
+            raise ValueError("values must have %d entries" % self.n)
+        _shim_call(_lib().gpb_hip_dev_from_host(self.p, _p(v), C.c_uint64(8 * self.n)))
+        return self
+
     def __del__(self):
         try:
             if self.p.value:
@@ -746,6 +753,120 @@ class HistBuilder(object):
             _shim_call(_lib().gpb_hip_hist_last_tree_cat_nodes(self.h, C.c_int(k - 1), _p(nic, C.c_int), _p(ncb, C.c_uint32)))
         out["node_is_cat"] = nic[:k - 1].copy(); out["node_cat_bits"] = ncb[:k - 1].copy()
         return out
+
+    # ---- tree scoring: leaf of a binned row, score += leaf value (out-of-bag rows, a validation matrix, new data) ----
+    @staticmethod
+    def node_go_left_mask(max_bin, default_bin, most_freq_bin, missing_type, default_left, threshold, cat_bits=None):
+        """-> 8 words: bit b = does STORED bin b of the column go left at this node (the rule of split_leaf; cat_bits: a categorical node's set).
+        max_bin = stored bins of the column - 1.  Host only: needs no handle and no device."""
+        w = None if cat_bits is None else np.ascontiguousarray(cat_bits, dtype=np.uint32)
+        if w is not None and w.size != 8:
+            raise ValueError("cat_bits must have 8 words")
+        out = np.zeros(8, dtype=np.uint32)
+        _shim_call(_lib().gpb_hip_hist_node_go_left_mask(C.c_int(int(max_bin)), C.c_int(int(default_bin)), C.c_int(int(most_freq_bin)), C.c_int(int(missing_type)),
+                                                         C.c_int(int(bool(default_left))), C.c_uint(int(threshold)), _p(w, C.c_uint32), _p(out, C.c_uint32)))
+        return out
+
+    def add_tree(self, tree, shrinkage=1.0):
+        """Stores a tree given as what grow_tree returns (or the same arrays of a reference tree) -> its id.  Leaf values are stored as
+        leaf_value * shrinkage."""
+        k = int(tree["num_leaves"])
+        ia = {key: np.ascontiguousarray(np.asarray(tree[key])[:max(k - 1, 0)], dtype=np.int32) for key in ("split_feature_inner", "default_left", "left_child", "right_child")}
+        thr = np.ascontiguousarray(np.asarray(tree["threshold_in_bin"])[:max(k - 1, 0)], dtype=np.uint32)
+        lv = np.ascontiguousarray(np.asarray(tree["leaf_value"])[:k], dtype=np.float64)
+        nic = ncb = None
+        if tree.get("node_is_cat") is not None:
+            nic = np.ascontiguousarray(np.asarray(tree["node_is_cat"])[:max(k - 1, 0)], dtype=np.int32)
+        if tree.get("node_cat_bits") is not None:
+            ncb = np.ascontiguousarray(np.asarray(tree["node_cat_bits"]).reshape(-1, 8)[:max(k - 1, 0)], dtype=np.uint32)
+        tid = C.c_int(-1)
+        _shim_call(_lib().gpb_hip_hist_forest_add_tree(self.h, C.c_int(k), _p(ia["split_feature_inner"], C.c_int), _p(thr, C.c_uint32), _p(ia["default_left"], C.c_int),
+                                                       _p(ia["left_child"], C.c_int), _p(ia["right_child"], C.c_int), _p(nic, C.c_int), _p(ncb, C.c_uint32), _p(lv),
+                                                       C.c_double(shrinkage), C.byref(tid)))
+        return tid.value
+
+    def keep_last_tree(self, shrinkage=1.0):
+        """Stores the last tree grow_tree has grown on this handle -> its id."""
+        tid = C.c_int(-1)
+        _shim_call(_lib().gpb_hip_hist_forest_keep_last_tree(self.h, C.c_double(shrinkage), C.byref(tid)))
+        return tid.value
+
+    def forest_size(self):
+        k = C.c_int(0)
+        _shim_call(_lib().gpb_hip_hist_forest_size(self.h, C.byref(k)))
+        return k.value
+
+    def forest_clear(self):
+        _shim_call(_lib().gpb_hip_hist_forest_clear(self.h))
+
+    def set_pred_bins(self, bins=None):
+        """Attaches a second matrix (F, n_pred) uint8, feature-major, binned with the training data's mappers; None detaches."""
+        if bins is None:
+            _shim_call(_lib().gpb_hip_hist_set_pred_bins(self.h, C.c_int(0), None))
+            self.n_pred = 0
+            return
+        b = np.ascontiguousarray(bins, dtype=np.uint8)
+        if b.ndim != 2 or b.shape[0] != self.F:
+            raise ValueError("bins must be (F, n_pred)")
+        _shim_call(_lib().gpb_hip_hist_set_pred_bins(self.h, C.c_int(b.shape[1]), _p(b, C.c_uint8)))
+        self.n_pred = b.shape[1]
+
+    def _score_rows(self, rows, pred):
+        n = getattr(self, "n_pred", 0) if pred else self.n
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        return n, r, (n if r is None else r.size)
+
+    def predict_leaf(self, tree_id, rows=None, pred=False):
+        """-> leaf of every listed row (None: all rows) of the training matrix or, pred=True, of the attached one in the stored tree tree_id."""
+        n, r, cnt = self._score_rows(rows, pred)
+        out = np.empty(cnt, dtype=np.int32)
+        if r is not None and cnt == 0:
+            return out
+        _shim_call(_lib().gpb_hip_hist_predict_leaf(self.h, C.c_int(int(bool(pred))), C.c_int(int(tree_id)), _p(r, C.c_int), C.c_int(cnt), _p(out, C.c_int)))
+        return out
+
+    def _tree_range(self, trees):
+        if trees is None:
+            return 0, self.forest_size()
+        if isinstance(trees, (int, np.integer)):
+            return int(trees), int(trees) + 1
+        return int(trees[0]), int(trees[1])
+
+    def add_score(self, score, trees=None, rows=None, pred=False):
+        """score (float64, one entry per row of the matrix) += the leaf values of the stored trees `trees` (None: all; an id; (begin, end)) for the listed
+        rows (None: all), in place, in tree order; every occurrence in rows adds once."""
+        n, r, cnt = self._score_rows(rows, pred)
+        if not (isinstance(score, np.ndarray) and score.dtype == np.float64 and score.flags.c_contiguous and score.flags.writeable):
+            raise ValueError("score must be a writable contiguous float64 array (it is updated in place)")
+        if score.size != n and not (pred and n == 0):
+            raise ValueError("score must have one entry per row of the matrix")
+        t0, t1 = self._tree_range(trees)
+        if r is not None and cnt == 0:
+            return score
+        _shim_call(_lib().gpb_hip_hist_add_score(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(score)))
+        return score
+
+    def add_score_dev(self, score_dev_ptr, trees=None, rows=None, pred=False):
+        """add_score on a device array (e.g. a float64 torch tensor's data_ptr()) over all rows of the matrix, enqueued on the handle's stream: nothing is copied and
+        nothing waited for; sync() waits for the stream."""
+        n, r, cnt = self._score_rows(rows, pred)
+        t0, t1 = self._tree_range(trees)
+        if r is not None and cnt == 0:
+            return
+        _shim_call(_lib().gpb_hip_hist_add_score_dev(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+                                                     C.c_void_p(int(score_dev_ptr))))
+
+    def add_score_bench(self, score_dev_ptr, trees=None, rows=None, pred=False, reps=20):
+        """mean ms of one add_score_dev launch (HIP events; one warm-up launch first).  The scores end up with reps + 1 updates."""
+        n, r, cnt = self._score_rows(rows, pred)
+        t0, t1 = self._tree_range(trees)
+        ms = C.c_double(0)
+        _shim_call(_lib().gpb_hip_hist_add_score_bench(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+                                                       C.c_void_p(int(score_dev_ptr)), C.c_int(int(reps)), C.byref(ms)))
+        return ms.value
+
+    def sync(self):
+        _shim_call(_lib().gpb_hip_hist_sync(self.h))
 
     def get_slot(self, slot):
         out = np.empty((self.total_bins, 2))

@@ -60,10 +60,11 @@ GPB_HIP_EXPORT int gpb_hip_set_device(int device);
 /* 1 if the current device is gfx950 */
 GPB_HIP_EXPORT int gpb_hip_device_is_gfx950(int* yes);
 /* Plain device-buffer helpers for hosts that have no allocator of their own (the "_dev" entry points take such
- * pointers; a torch/RCCL host passes tensor.data_ptr() instead). gpb_hip_dev_to_host synchronises the device first. */
+ * pointers; a torch/RCCL host passes tensor.data_ptr() instead). gpb_hip_dev_to_host / _from_host synchronise the device first. */
 GPB_HIP_EXPORT int gpb_hip_dev_alloc(uint64_t bytes, void** out);
 GPB_HIP_EXPORT int gpb_hip_dev_free(void* p);
 GPB_HIP_EXPORT int gpb_hip_dev_to_host(void* dst_host, const void* src_dev, uint64_t bytes);
+GPB_HIP_EXPORT int gpb_hip_dev_from_host(void* dst_dev, const void* src_host, uint64_t bytes);
 /* Runs the fp64-DPP primitives against their compiler-scheduled equivalents on the device. */
 GPB_HIP_EXPORT int gpb_hip_selftest(void);
 /* Test entry: ONE block operation of the low-rank preconditioners ("pivoted_cholesky" / "fitc" / full-scale Vecchia) on host data, sized and launched as the model path
@@ -732,6 +733,58 @@ GPB_HIP_EXPORT int gpb_hip_hist_find_best_split(gpb_hip_hist_t* h, int32_t slot,
                                                 double min_gain_to_split, const int8_t* is_feature_used, int32_t* best_feature,
                                                 double* per_feature_out10, int32_t* per_feature_default_left,
                                                 int32_t* per_feature_splittable);
+
+/* Tree scoring on the device: which leaf does a BINNED row fall into, and score[row] += leaf value over a range of stored trees -- for rows outside a
+ * tree's own root (out-of-bag rows), a validation matrix, new data.  Stands in for Tree::AddPredictionToScore on binned data (src/LightGBM/io/tree.cpp:147,
+ * :226) with Tree::DecisionInner per node (include/LightGBM/tree.h:349-409), as GBDT::UpdateScore calls it for every new tree
+ * (src/LightGBM/boosting/gbdt.cpp:606-623; ScoreUpdater::AddScore, score_updater.hpp:93-96 validation sets, :118-122 out-of-bag rows).  Prediction from raw
+ * feature values (Tree::Decision) is not part of it.  With a communicator on the handle nothing is exchanged: every rank scores its own rows with its
+ * own copy of the forest.
+ *   node_go_left_mask   host only, no device needed: the 256-bit set (8 words, bit b = STORED bin b of the column) of the bins a node sends left -- the rule of
+ *                       gpb_hip_hist_split_leaf / _split_leaf_categorical (DenseBin::SplitInner / SplitCategoricalInner, dense_bin.hpp:176-342, single-feature
+ *                       group) for stored bins 0 .. 255.  max_bin = stored bins of the column - 1; cat_bits8 == NULL: numerical node.
+ *   forest_add_tree     stores a tree given as the arrays gpb_hip_hist_grow_tree returns -- or the arrays of a reference Tree (include/LightGBM/tree.h), same
+ *                       conventions: children ~leaf for leaves, threshold_in_bin of a categorical node = its running index, node_cat_bits8 = 8 words per
+ *                       NODE (bit b = the feature's bin b; Tree::SplitCategorical's cat_threshold_inner_, tree.cpp:76-108).  node_is_cat / node_cat_bits8 may be
+ *                       NULL for a tree without categorical nodes.  Per column max_bin, default_bin, most_freq_bin and missing type come from
+ *                       gpb_hip_hist_set_fix_info / _set_split_info, as for gpb_hip_hist_split_leaf: both must have been called.  The stored leaf values are
+ *                       leaf_value * shrinkage, rounded once (Tree::Shrinkage, tree.h:188).  num_leaves = 1 is a tree without nodes.  The tree is validated:
+ *                       columns < F; every child ~leaf with leaf < num_leaves or a LATER node; every node but the root and every leaf referenced exactly once;
+ *                       a categorical node has a set; at most 439 leaves (one tree's tables must fit a chunk of LDS).  *tree_id: its index, 0, 1, ...
+ *   forest_keep_last_tree  the same for the last tree gpb_hip_hist_grow_tree has grown on the handle (the handle keeps its arrays and categorical sets)
+ *   forest_size / forest_clear   number of stored trees / drop them all (ids start at 0 again)
+ *   set_pred_bins       attaches a second matrix: F x n_pred uint8, feature-major, binned with the SAME mappers as the training data (what a validation
+ *                       Dataset aligned with the training Dataset holds); NULL or n_pred <= 0 detaches
+ *   predict_leaf        leaf_out[i] = leaf of rows[i] in tree tree_id; which: 0 the training rows, 1 the attached matrix; rows == NULL: all rows (cnt ignored)
+ *   add_score           score: HOST array over ALL rows of the matrix; score[rows[i]] += value_t[leaf_t(rows[i])] for t = tree_begin .. tree_end - 1, strictly
+ *                       in tree order, once per OCCURRENCE in rows, without fused multiply-adds: bit-identical to the host loop
+ *                       for t: for i: score[rows[i]] += value_t[leaf_t[rows[i]]]  (Tree::AddPredictionToScore(data, data_indices, cnt, score)), and independent
+ *                       of how the range is split over calls.  Entries not named by rows keep their bits.
+ *   add_score_dev       the same with score a DEVICE array, enqueued on the handle's stream: no copy of the scores and no synchronisation (the pattern of
+ *                       gpb_hip_vecchia_nll_terms_dev); rows stays a host list (checked, then staged through pinned memory on the stream).
+ *                       gpb_hip_hist_sync waits for the handle's stream.
+ * Every refusal (unknown tree id or empty range, which = 1 with nothing attached, a row index outside the matrix, an invalid tree, rows wider than 560 padded
+ * columns) is -1 with a message before any kernel is launched. */
+GPB_HIP_EXPORT int gpb_hip_hist_node_go_left_mask(int32_t max_bin, int32_t default_bin, int32_t most_freq_bin, int32_t missing_type, int32_t default_left,
+                                                  uint32_t threshold, const uint32_t* cat_bits8, uint32_t* mask8_out);
+GPB_HIP_EXPORT int gpb_hip_hist_forest_add_tree(gpb_hip_hist_t* h, int32_t num_leaves, const int32_t* split_feature_inner, const uint32_t* threshold_in_bin,
+                                                const int32_t* default_left, const int32_t* left_child, const int32_t* right_child,
+                                                const int32_t* node_is_cat, const uint32_t* node_cat_bits8, const double* leaf_value, double shrinkage,
+                                                int32_t* tree_id);
+GPB_HIP_EXPORT int gpb_hip_hist_forest_keep_last_tree(gpb_hip_hist_t* h, double shrinkage, int32_t* tree_id);
+GPB_HIP_EXPORT int gpb_hip_hist_forest_size(gpb_hip_hist_t* h, int32_t* num_trees);
+GPB_HIP_EXPORT int gpb_hip_hist_forest_clear(gpb_hip_hist_t* h);
+GPB_HIP_EXPORT int gpb_hip_hist_set_pred_bins(gpb_hip_hist_t* h, int32_t n_pred, const uint8_t* bins_fm);
+GPB_HIP_EXPORT int gpb_hip_hist_predict_leaf(gpb_hip_hist_t* h, int32_t which, int32_t tree_id, const int32_t* rows, int32_t cnt, int32_t* leaf_out);
+GPB_HIP_EXPORT int gpb_hip_hist_add_score(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                          double* score);
+GPB_HIP_EXPORT int gpb_hip_hist_add_score_dev(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                              double* score_dev);
+GPB_HIP_EXPORT int gpb_hip_hist_sync(gpb_hip_hist_t* h);
+/* Measurement helper (as gpb_hip_hist_bench): one gpb_hip_hist_add_score_dev as warm-up, then `reps` more launches of the same kernel between two HIP events on the
+ * handle's stream; *ms_avg = their mean.  The scores end up with reps + 1 updates. */
+GPB_HIP_EXPORT int gpb_hip_hist_add_score_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                                double* score_dev, int32_t reps, double* ms_avg);
 
 #ifdef __cplusplus
 }
