@@ -48,6 +48,20 @@ __device__ __forceinline__ double row_bcast(double x) {
                : "v"(x), "n"(LANE));
   return r;
 }
+// The same without the wait states, for a source that was written several instructions earlier (the hazard check covers it like the fmacs).
+template <int LANE>
+__device__ __forceinline__ double row_bcast_nopad(double x) {
+  static_assert(LANE >= 0 && LANE < 16, "row_newbcast lane");
+#ifdef GPB_DPP_PAD_EVERY_FMAC
+  return row_bcast<LANE>(x);
+#else
+  double r;
+  asm volatile("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf"
+               : "=v"(r)
+               : "v"(x), "n"(LANE));
+  return r;
+#endif
+}
 // acc -= bcast<LANE>(b) * own      (one v_fmac_f64 with the broadcast folded in)
 template <int LANE>
 __device__ __forceinline__ void row_fnma(double& acc, double b, double own) {
@@ -84,6 +98,17 @@ __device__ __forceinline__ double row_sum16(double v) {
   v += dpp_move_f64<0x141>(v);
   v += dpp_move_f64<0x140>(v);
   return v;
+}
+// ---- LDS by address -------------------------------------------------------------------------------------------------
+// A 32-bit LDS address as a pointer the compiler reads with ds_read and no base register (the low 32 bits of a generic pointer into LDS are that address).
+using LdsDouble = __attribute__((address_space(3))) double;
+__device__ __forceinline__ const LdsDouble* lds_doubles_at(unsigned addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (const LdsDouble*)addr;
+#else
+  (void)addr;
+  return nullptr;
+#endif
 }
 // ---- compile-time lane sets ------------------------------------------------------------------------------------------
 // A workgroup's thread t is lane t % 64 of its wavefront and lane l = t % 16 of its point's DPP row, so "l in S" for a compile-time set
@@ -135,9 +160,11 @@ __device__ __forceinline__ double row_bcast_builtin(double x) {
 }
 #ifdef GPB_DPP_VIA_BUILTIN
 #define GPB_ROW_BCAST(L, x) ::gpb::row_bcast_builtin<L>(x)
+#define GPB_ROW_BCAST_NOPAD(L, x) ::gpb::row_bcast_builtin<L>(x)
 #define GPB_ROW_FNMA(L, acc, b, own) (acc) = __builtin_fma(-::gpb::row_bcast_builtin<L>(b), (own), (acc))
 #else
 #define GPB_ROW_BCAST(L, x) ::gpb::row_bcast<L>(x)
+#define GPB_ROW_BCAST_NOPAD(L, x) ::gpb::row_bcast_nopad<L>(x)
 #define GPB_ROW_FNMA(L, acc, b, own) ::gpb::row_fnma<L>((acc), (b), (own))
 #endif
 

@@ -165,6 +165,11 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
   constexpr int NP = (MODE == MODE_GRAD) ? GPB_NUM_PARTIALS : 3;
 
   using Rec = RecT<D3>;
+  // The instances with two register slots (MT = 20, 30: right-looking in every mode, the metric instance among them) shed the part of a trip that is not
+  // arithmetic -- see the four places below that test kLeanTrip.  The other instances keep the code they had: their register budgets are spent
+  // (MT = 10 sits at 64 VGPRs = eight wavefronts per SIMD, MT >= 50 spills in the solving modes), and the allocator answers any change there.
+  constexpr bool kLeanTrip = (NS == 2);
+  static_assert(!kLeanTrip || !kLeftLooking, "two slots: MT <= 30, right-looking");
   // MODE_GRAD with MT <= 30: d/dlog(a) of every kernel entry is kept in LDS from the assembly pass ([step][thread]: conflict-free,
   // 31 x 256 x 8 B = 62 KB for MT = 30, two workgroups per CU) so that the contraction pass evaluates no exp; larger MT re-evaluate.
   constexpr bool kStoreDK = (MODE == MODE_GRAD) && (MT <= 30);
@@ -188,6 +193,15 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
   static_assert(PBYTES % 16 == 0 && PBYTES >= 16 * (NS * 16), "record block: 16-byte aligned, room for the (A, b) pairs");
   __shared__ double2 s_ab[(MODE == MODE_GRAD && !kStoreDK) ? 16 : 1][(MODE == MODE_GRAD && !kStoreDK) ? NS * 16 : 1];
   double dk_last = 0.0;
+  // Pair steps (two register slots, likelihood and factor modes): the two LDS addresses a lane reads in step j -- its row's record and its column's record,
+  // both functions of (j, lane, point) only -- wait in LDS as 16-bit LDS addresses (absolute: the read needs no base added), written once per workgroup,
+  // [step][row | column][thread].
+  // A step then issues two ds_read_u16 instead of two selects, an add and a multiply-add on the VALU, which is the unit the kernel is bound by.
+  // (MODE_GRAD with stored derivatives has no LDS to spare; the instances with four slots are not register-resident anyway.)
+  constexpr bool kPairTab = kLeanTrip && MODE != MODE_GRAD;
+  constexpr int NPAIR = kPairTab ? ((MT - 16 < 15) ? MT - 16 : 15) : 0;      // pair steps: columns 16 .. min(MT - 1, 30)
+  // (a workgroup's share of the LDS is at most 64 KB: its addresses fit 16 bits)
+  __shared__ unsigned short s_pair[NPAIR > 0 ? NPAIR : 1][2][NPAIR > 0 ? 256 : 1];
 
   __shared__ double s_tot[GPB_NUM_PARTIALS];          // this workgroup's sums over all its groups of 16 points
   __shared__ double s_fin[GPB_NUM_PARTIALS][4];
@@ -205,6 +219,17 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
   __shared__ double s_pm[16];
   __shared__ int s_pe[16];
   if (tid0 < 16) { s_pm[tid0] = 0.5; s_pe[tid0] = 1; }   // 0.5 * 2^1 = 1
+  if constexpr (NPAIR > 0) {      // (every thread reads back only what it wrote itself: no barrier)
+    const int g0 = tid0 >> 4, l0 = tid0 & 15;
+    static_for<0, NPAIR>([&](auto j_) {
+      constexpr int j = decltype(j_)::value;
+      const bool upper = l0 <= 14 - j;                    // lanes l <= J = 14 - j: entry (slot 1, column 16 + j); the others: (slot 0, column 14 - j)
+      const int row = upper ? 31 - l0 : l0, col = upper ? 16 + j : 14 - j;
+      // (the low 32 bits of a generic pointer into LDS are the LDS address)
+      s_pair[j][0][tid0] = (unsigned short)(size_t)(s_pts_raw + g0 * PBYTES + row * (int)sizeof(Rec));
+      s_pair[j][1][tid0] = (unsigned short)(size_t)(s_pts_raw + g0 * PBYTES + col * (int)sizeof(Rec));
+    });
+  }
 
   // PERSISTENT workgroups: the grid is one resident round of workgroups (host: occupancy x CUs, trimmed so that every workgroup makes
   // the same number of trips +- 1); workgroup b takes the groups b, b + G, b + 2 G, ... of 16 points.  The table set-up, the kernel-argument
@@ -214,22 +239,52 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
   // every gather is gone.  (Measured and dropped: a start delay hashed from the workgroup id, to de-correlate the phases of workgroups that
   // all start together and make equally long trips -- no gain.  What does matter is the NUMBER of workgroups: with exactly one resident
   // round every workgroup runs start to end on "its" CU and the slowest CU sets the time; several rounds balance -- see persistent_grid.)
+  // Unweighted, right-looking: row 0's diagonal is the uniform diag_nn in every point, so the first sweep's reciprocal is taken here, once per workgroup,
+  // by the same three device operations, and kept in a scalar register pair.
+  constexpr bool kFirstInv = !WT && kLeanTrip;
+  double inv_first = 0.0;
+  if constexpr (kFirstInv) {
+    const long long b = __builtin_bit_cast(long long, fast_rcp(args.diag_nn));
+    const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+    inv_first = __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned int)lo);
+  }
   const int m = args.m;
+  // Index and own-record loads: 32-bit byte offsets against a base that is uniform in the workgroup -- the group's first row of the neighbour table, its
+  // first record -- formed per trip on the scalar unit.  What remains per lane is (point within the group) * m + row: one 32-bit multiply-add and a shift
+  // instead of a 64-bit multiply, shift and add pieced together from halves, and it holds for tables of any size.  Rows past the shard's end are clamped
+  // to its last point as before (only the last group has any): `last` = index within the group of the last point inside the shard.
+  auto group_first = [&](int grp_) -> long long { return (long long)args.i_begin + (long long)grp_ * 16; };
+  auto group_last = [&](int grp_) -> int { const long long rem = (long long)args.i_end - group_first(grp_) - 1; return rem < 15 ? (int)rem : 15; };
   auto fetch_idx = [&](int grp_, int tid_, int (&out)[NS]) {
     const int g_ = tid_ >> 4, l_ = tid_ & 15;
-    const long long ir = (long long)args.i_begin + (long long)grp_ * 16 + g_;
-    const int ii = ir < (long long)args.i_end ? (int)ir : args.i_end - 1;
+    if constexpr (kLeanTrip) {
+      const long long first = group_first(grp_);
+      const int last = group_last(grp_);
+      const int gc = g_ < last ? g_ : last;
+      const char* rows = reinterpret_cast<const char*>(args.nn + (size_t)first * (size_t)m);
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const int r = 16 * s + ((s & 1) ? 15 - l_ : l_);
-      int idx = -1;
-      if (r < m) idx = args.nn[(size_t)ii * m + r];
-      else if (r == MT) idx = ii;
-      out[s] = idx;
+      for (int s = 0; s < NS; ++s) {
+        const int r = 16 * s + ((s & 1) ? 15 - l_ : l_);
+        int idx = -1;
+        if (r < m) idx = *reinterpret_cast<const int*>(rows + ((unsigned)gc * (unsigned)m + (unsigned)r) * 4u);
+        else if (r == MT) idx = (int)first + gc;
+        out[s] = idx;
+      }
+    } else {
+      const long long ir = (long long)args.i_begin + (long long)grp_ * 16 + g_;
+      const int ii = ir < (long long)args.i_end ? (int)ir : args.i_end - 1;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int r = 16 * s + ((s & 1) ? 15 - l_ : l_);
+        int idx = -1;
+        if (r < m) idx = args.nn[(size_t)ii * m + r];
+        else if (r == MT) idx = ii;
+        out[s] = idx;
+      }
     }
   };
   int nidx[NS];
-  fetch_idx(blockIdx.x, tid0, nidx);
+  if (!kLeanTrip || (int)blockIdx.x < args.ngroups) fetch_idx(blockIdx.x, tid0, nidx);      // (the grid never has more workers than groups; the lean form's addresses rely on it)
   for (int grp = blockIdx.x; grp < args.ngroups; grp += G) {
   // the thread index is made opaque once per trip: everything derived from it (row indices, LDS offsets, dummy coordinates, lane
   // predicates: ~35 VGPRs' worth) is then recomputed per trip -- as the one-group-per-workgroup kernel did -- instead of being hoisted
@@ -238,9 +293,18 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
   asm volatile("; per-trip thread index" : "+v"(tid));
   const int g = tid >> 4;   // point within the workgroup
   const int l = tid & 15;   // lane within the point's DPP row
-  const long long i_raw = (long long)args.i_begin + (long long)grp * 16 + g;
-  const bool active = i_raw < (long long)args.i_end;
-  const int i = active ? (int)i_raw : args.i_end - 1;   // inactive groups redo the last point, contribute 0
+  bool active;
+  int i, g_in = 0;                                      // inactive groups redo the last point, contribute 0
+  if constexpr (kLeanTrip) {
+    const int g_last = group_last(grp);
+    active = g <= g_last;
+    g_in = active ? g : g_last;
+    i = (int)group_first(grp) + g_in;
+  } else {
+    const long long i_raw = (long long)args.i_begin + (long long)grp * 16 + g;
+    active = i_raw < (long long)args.i_end;
+    i = active ? (int)i_raw : args.i_end - 1;
+  }
   int cidx[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) cidx[s] = nidx[s];
@@ -249,7 +313,9 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
 
   // ---- gather the rows' records: centred on the point (differences of nearby points stay accurate for
   //      coordinates with a large offset), scaled, staged in LDS for the column operands ------------------
-  const double4 ctr = args.pts[i];
+  double4 ctr;
+  if constexpr (kLeanTrip) ctr = *reinterpret_cast<const double4*>(reinterpret_cast<const char*>(args.pts + group_first(grp)) + (unsigned)g_in * 32u);
+  else ctr = args.pts[i];
   Rec own[NS];
   // sample weights (Gaussian likelihood: observation-specific nugget 1 / w on the transformed scale, GetGaussianNuggetDiagFromWeights,
   // re_model_template.h:6393-6417; Vecchia_utils.cpp:1418-1422, 1610-1614): own_dg[s] = diagonal entry of this lane's row of slot s
@@ -280,6 +346,9 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
       p.x = (q.x - ctr.x) * sc; p.y = (q.y - ctr.y) * sc; p.w = q.w;
       if constexpr (D3) p.z = (q.z - ctr.z) * sc;
     } else {
+      // (an asm statement keeps the branch around this block: a wavefront without a dummy row -- m == MT and i >= m, nearly all of them -- skips
+      //  the conversion and the multiply instead of issuing them under an empty exec mask)
+      if constexpr (kLeanTrip) asm volatile("; dummy rows");
       p.x = kDummyCoord * (double)(r + 1); p.y = 0.0; p.w = 0.0;
       if constexpr (D3) p.z = 0.0;
     }
@@ -391,10 +460,20 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
         // lanes l <= J: entry (slot sA, column cA); lanes l > J: entry (slot sB, column cB).  Both records come from LDS through
         // per-lane addresses picked with a constant lane mask (2 selects instead of 1 compare + 5 selects per step).
         constexpr unsigned long long MA = row_lanes_le(J);
-        const int ro = sel_lanes<MA>(row_off[sA], row_off[sB], grp);
-        const int co = sel_lanes_const<MA, cA, cB>(grp) * (int)sizeof(Rec);
-        const Rec o = *reinterpret_cast<const Rec*>(reinterpret_cast<const char*>(gp) + ro);
-        const Rec q = *reinterpret_cast<const Rec*>(reinterpret_cast<const char*>(gp) + co);
+        Rec o, q;
+        if constexpr (kPairTab) {
+          static_assert(sA == 1 && sB == 0 && J == 14 - (cA - 16) && cB == J, "s_pair is filled for this enumeration of the pair steps");
+          const LdsDouble* po = lds_doubles_at(s_pair[cA - 16][0][tid]);
+          const LdsDouble* pq = lds_doubles_at(s_pair[cA - 16][1][tid]);
+          o.x = po[0]; o.y = po[1]; q.x = pq[0]; q.y = pq[1];
+          if constexpr (D3) { o.z = po[2]; q.z = pq[2]; }
+          o.w = 0.0; q.w = 0.0;        // (an evaluation reads coordinates only)
+        } else {
+          const int ro = sel_lanes<MA>(row_off[sA], row_off[sB], grp);
+          const int co = sel_lanes_const<MA, cA, cB>(grp) * (int)sizeof(Rec);
+          o = *reinterpret_cast<const Rec*>(reinterpret_cast<const char*>(gp) + ro);
+          q = *reinterpret_cast<const Rec*>(reinterpret_cast<const char*>(gp) + co);
+        }
         const double v = eval_entry(o, q, e_);
         M[sA][cA] = v;    // lanes of the other half hold entries above the diagonal there: never read
         M[sB][cB] = v;
@@ -430,8 +509,12 @@ __global__ __launch_bounds__(256, (MT > 30 && MT <= 40 && MODE != MODE_NLL) ? 2 
     // column-k registers become DPP sources in this sweep: fence them (they were last written by the assembly
     // for k == 0, by sweep k-1's first fmacs otherwise -- the verifier checks the generated code either way)
     if constexpr (k == 0) static_for<0, NS>([&](auto s_) { dpp_fence(M[decltype(s_)::value][0]); });
-    const double piv = GPB_ROW_BCAST(lk, M[sk][k]);
-    const double inv = fast_rcp(piv);
+    double inv;
+    if constexpr (kFirstInv && k == 0) inv = inv_first;
+    // The pivot was last written by the FIRST fmacs of the sweep before (column k comes first there) -- the rest of that sweep lies between, so the
+    // broadcast needs no wait states of its own, except where that rest is shorter than two instructions: the last two sweeps.  (Checked on the ISA at build.)
+    else if constexpr (kLeanTrip && k >= 1 && k <= MT - 3) inv = fast_rcp(GPB_ROW_BCAST_NOPAD(lk, M[sk][k]));
+    else inv = fast_rcp(GPB_ROW_BCAST(lk, M[sk][k]));
     double T[NS];
     static_for<sk, NS>([&](auto s_) { T[decltype(s_)::value] = M[decltype(s_)::value][k] * inv; });
     static_for<k + 1, MT + 1>([&](auto c_) {

@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Instruction mix of one kernel in a gfx950 .s file (hipcc -save-temps): counts per mnemonic and per class, straight-line body.
 
-    python scripts/isa_mix.py <file.s> <kernel-name-substring> [--top N]
+    python scripts/isa_mix.py <file.s> <kernel-name-substring> [--top N] [--trip]
+
+--trip: only the basic blocks of ONE trip of vecchia_point_kernel's persistent loop (from the loop header that carries the "per-trip thread index" marker
+to the loop's exit block); branches not taken by a full-length row are still counted -- the count is static.
 """
 import collections
 import re
@@ -39,7 +42,14 @@ def main():
         raise SystemExit("kernel not found")
     ops = collections.Counter(); cls = collections.Counter()
     meta = {}
-    for l in lines[start + 1:]:
+    body = lines[start + 1:]
+    if "--trip" in sys.argv:
+        at = next(i for i, l in enumerate(body) if "per-trip thread index" in l)
+        while not re.match(r"^\.LBB\d+_\d+:", body[at]): at -= 1
+        end = next(i for i in range(at, len(body)) if "%._crit_edge" in body[i])
+        body = body[at:end] + [".end_amdhsa_kernel"]
+        print("one trip: lines %d-%d of the kernel, %d wait states in s_nop" % (at + 1, end, sum(int(l.split()[1], 0) + 1 for l in body if l.strip().startswith("s_nop"))))
+    for l in body:
         t = l.strip()
         if t.startswith(".end_amdhsa_kernel") or t.startswith(".Lfunc_end"):
             break
