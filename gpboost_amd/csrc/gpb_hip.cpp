@@ -372,7 +372,9 @@ struct gpb_hip_vecchia {
   double* d_vdC = nullptr; double* d_vQdC = nullptr; double* d_vX1 = nullptr; double* d_vV1 = nullptr; double* d_vX2 = nullptr; double* d_vHm = nullptr;
   double* d_vw = nullptr; double* d_vv = nullptr; double* d_vz = nullptr; double* d_vdA = nullptr; double* d_vdD = nullptr;
   bool vif_has_grad_inputs = false, vif_has_grad_factor = false;
-  std::vector<double> vif_ip_host;      // the inducing points [k][3] on the host (the k x k matrices of the VIF-Laplace path are built there, gpb_laplace.inc)
+  int vif_stage = 0;              // what the read-only test seam (gpb_hip_vecchia_vif_get_matrix / _get_point_terms) may copy: 0 nothing, 1 the buffers of the last
+                                  // gpb_hip_vecchia_vif_factor, 2 also those of the last gpb_hip_vecchia_vif_grad_sums; every residual-process factor launch resets it
+  std::vector<double> vif_ip_host;     // the inducing points [k][3] on the host (the k x k matrices of the VIF-Laplace path are built there, gpb_laplace.inc)
   int* d_leaf = nullptr; double* d_leaf_part = nullptr; double* d_leaf_out = nullptr; size_t leaf_part_cap = 0;
   LaplaceState* lap = nullptr;
   GpbComm comm;                   // optional: in-library all-reduce of the partial terms (gpb_hip_vecchia_comm_init / _comm_init_local)
@@ -389,7 +391,7 @@ static void vif_free(gpb_hip_vecchia* h) {
   dev_free(h->d_ip); dev_free(h->d_V); dev_free(h->d_vif_part); dev_free(h->d_vC); dev_free(h->d_vQ); dev_free(h->d_vM); dev_free(h->d_vG); dev_free(h->d_vgpart);
   dev_free(h->d_vout); dev_free(h->d_vdC); dev_free(h->d_vQdC); dev_free(h->d_vX1); dev_free(h->d_vV1); dev_free(h->d_vX2); dev_free(h->d_vHm); dev_free(h->d_vw);
   dev_free(h->d_vv); dev_free(h->d_vz); dev_free(h->d_vdA); dev_free(h->d_vdD);
-  h->vif_has_grad_inputs = h->vif_has_grad_factor = false;
+  h->vif_has_grad_inputs = h->vif_has_grad_factor = false; h->vif_stage = 0;
 }
 
 struct gpb_hip_exact {
@@ -804,7 +806,7 @@ int gpb_hip_vecchia_set_shard(gpb_hip_vecchia_t* h, int32_t i_begin, int32_t i_e
 // parameters (CalcGradientF, re_model_template.h:3313-3316).  The full-scale factor carries the response inside Q, v, z: that one goes.
 static void response_changed(gpb_hip_vecchia_t* h) {
   h->has_yaux = false;
-  if (h->vif_k > 0) h->has_factor = false;
+  if (h->vif_k > 0) { h->has_factor = false; h->vif_stage = 0; }
   else if (h->has_factor) h->u_stale = true;
 }
 static int refresh_u(gpb_hip_vecchia_t* h) {
@@ -1510,7 +1512,7 @@ int gpb_hip_vecchia_vif_set_inducing_points(gpb_hip_vecchia_t* h, int32_t k, con
   if (h->d > 3) return fail("full-scale Vecchia: coordinate dimensions 1..3 are on the HIP hot path (got %d)", h->d);
   HIP_OK(hipSetDevice(h->device));
   const int kp = (k | 1), kq = gpb::vif_kq(k);
-  if (gpb::vif_resid_lds_bytes(h->m, kq) > 150 * 1024) return fail("full-scale Vecchia: %d neighbours x %d inducing points exceed the LDS of a CU", h->m, k);
+  if (gpb::vif_resid_lds_bytes(h->m, kq) > gpb::vif_resid_lds_max()) return fail("full-scale Vecchia: %d neighbours x %d inducing points exceed the LDS of a CU", h->m, k);
   HIP_OK(hipStreamSynchronize(h->stream));
   vif_free(h);
   std::vector<double> ip3((size_t)k * 3, 0.0);
@@ -1544,6 +1546,7 @@ static int vif_upload_matrix(gpb_hip_vecchia_t* h, int slot, const double* src, 
 // Gaussian, Dp starts at 1 (Vecchia_utils.cpp:1873-1874) and the neighbours' diagonal gets + 1, the nugget (:1952-1960); latent, no nugget, their diagonal x 1 + 1e-10 (:1965-1967).
 static int vif_resid_factor(gpb_hip_vecchia_t* h, int i_begin, const double* Linv_rowmajor, int cov_type, double var, double a, bool latent, double* dC) {
   const int n = h->n, k = h->vif_k, kq = h->vif_kq;
+  h->vif_stage = 0;
   if (alloc_factor(h)) return -1;
   if (vif_upload_matrix(h, 0, Linv_rowmajor, true)) return -1;                   // V = C Linv'
   HIP_OK(gpb::launch_vif_crosscov(cov_type, h->d_pts, h->d_ip, 0, n, k, kq, h->d, var, a, h->d_vC, dC, h->stream));
@@ -1575,14 +1578,14 @@ int gpb_hip_vecchia_vif_factor(gpb_hip_vecchia_t* h, int cov_type, double var, d
   if (vif_resid_factor(h, 0, Linv_rowmajor, cov_type, var, a, false, with_grad ? h->d_vdC : nullptr)) return -1;
   HIP_OK(gpb::launch_reduce_partials(h->d_vif_part, n, 3, h->d_vout, nullptr, h->stream, nullptr));
   HIP_OK(gpb::launch_vif_spmm(h->d_A, h->d_nn, 0, n, h->m, kq, h->d_vC, h->d_vQ, with_grad ? h->d_vdC : nullptr, with_grad ? h->d_vQdC : nullptr, h->stream));
-  HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, kq, h->d_vgpart, h->d_vG, h->stream));
+  HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, k, kq, h->d_vgpart, h->d_vG, h->stream));
   double o[3];
   HIP_OK(hipMemcpyAsync(o, h->d_vout, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipMemcpy2DAsync(G_host, sizeof(double) * (size_t)(k + 1), h->d_vG, sizeof(double) * (size_t)kq, sizeof(double) * (size_t)(k + 1), (size_t)(k + 1),
                           hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   out3_host[0] = o[gpb::GPB_P_QUAD]; out3_host[1] = o[gpb::GPB_P_LOGDET]; out3_host[2] = o[gpb::GPB_P_BAD];
-  h->has_factor = true; h->vif_has_grad_inputs = with_grad != 0;
+  h->has_factor = true; h->vif_has_grad_inputs = with_grad != 0; h->vif_stage = 1;
   API_END();
 }
 
@@ -1595,7 +1598,9 @@ static int vif_grad_sums_impl(gpb_hip_vecchia_t* h, int cov_type, double var, do
 int gpb_hip_vecchia_vif_grad_sums(gpb_hip_vecchia_t* h, int cov_type, double var, double a, const double* Winv, const double* Si, const double* N0,
                                   const double* negMp1, const double* w_host, int keep_factor, double* sums12_host) {
   API_BEGIN();
+  if (h) h->vif_stage = h->vif_stage >= 1 ? 1 : 0;
   if (vif_grad_sums_impl(h, cov_type, var, a, Winv, Si, N0, negMp1, w_host, keep_factor, sums12_host, false)) return -1;
+  if (h->vif_stage == 1) h->vif_stage = 2;
   API_END();
 }
 // latent: the residual process of a NON-GAUSSIAN model (no nugget, the neighbours' diagonal x (1 + 1e-10); gpb_laplace.inc uses the derivative factors dA / dD only)
@@ -1655,6 +1660,41 @@ int gpb_hip_vecchia_vif_get_grad_factor(gpb_hip_vecchia_t* h, int p, double* dA_
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipMemcpy(dA_host, h->d_vdA + (size_t)p * h->n * h->m, sizeof(double) * (size_t)h->n * h->m, hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(dD_host, h->d_vdD + (size_t)p * h->n, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToHost));
+  API_END();
+}
+
+/* Read-only test seam of the full-scale Vecchia family (tests/test_zz_vif_kernels_gpu.py): copies only, after a stream synchronisation; no kernel is launched.
+   which: GPB_VIF_MAT_*; C, dC, V, Q, QdC, Hm, X1, V1, X2r: n x kq row-major; v, z: n; G: kq x kq. */
+int gpb_hip_vecchia_vif_get_matrix(gpb_hip_vecchia_t* h, int which, double* out_host) {
+  API_BEGIN();
+  if (!h || !out_host) return fail("null argument");
+  if (which < 0 || which > GPB_VIF_MAT_G) return fail("gpb_hip_vecchia_vif_get_matrix: which = %d (0..%d)", which, (int)GPB_VIF_MAT_G);
+  if (h->vif_k < 1) return fail("no inducing points have been set (call gpb_hip_vecchia_vif_set_inducing_points)");
+  const bool of_grad = which == GPB_VIF_MAT_HM || which == GPB_VIF_MAT_X1 || which == GPB_VIF_MAT_V1 || which == GPB_VIF_MAT_X2R || which == GPB_VIF_MAT_VEC_V ||
+                       which == GPB_VIF_MAT_VEC_Z;
+  const bool of_with_grad = which == GPB_VIF_MAT_DC || which == GPB_VIF_MAT_QDC;
+  if (of_grad && h->vif_stage < 2) return fail("gpb_hip_vecchia_vif_get_matrix(%d) needs gpb_hip_vecchia_vif_grad_sums first", which);
+  if (of_with_grad && (h->vif_stage < 1 || !h->vif_has_grad_inputs)) return fail("gpb_hip_vecchia_vif_get_matrix(%d) needs gpb_hip_vecchia_vif_factor(with_grad = 1) first", which);
+  if (h->vif_stage < 1) return fail("gpb_hip_vecchia_vif_get_matrix(%d) needs gpb_hip_vecchia_vif_factor first", which);
+  const double* src[] = {h->d_vC, h->d_vdC, h->d_V, h->d_vQ, h->d_vQdC, h->d_vHm, h->d_vX1, h->d_vV1, h->d_vX2, h->d_vv, h->d_vz, h->d_vG};
+  const size_t n = (size_t)h->n, kq = (size_t)h->vif_kq;
+  const size_t count = which == GPB_VIF_MAT_G ? kq * kq : ((which == GPB_VIF_MAT_VEC_V || which == GPB_VIF_MAT_VEC_Z) ? n : n * kq);
+  if (!src[which]) return fail("gpb_hip_vecchia_vif_get_matrix(%d): the buffer is not allocated", which);
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipMemcpy(out_host, src[which], sizeof(double) * count, hipMemcpyDeviceToHost));
+  API_END();
+}
+/* the per-point partials [nterms][n]: 3 ({GPB_P_*} order) after vif_factor, 12 ([2 * S + p]) after vif_grad_sums */
+int gpb_hip_vecchia_vif_get_point_terms(gpb_hip_vecchia_t* h, int nterms, double* out_host) {
+  API_BEGIN();
+  if (!h || !out_host) return fail("null argument");
+  if (nterms == 3) { if (h->vif_stage != 1) return fail("gpb_hip_vecchia_vif_get_point_terms(3) needs gpb_hip_vecchia_vif_factor as the last full-scale Vecchia call"); }
+  else if (nterms == GPB_VIF_GRAD_TERMS) { if (h->vif_stage != 2) return fail("gpb_hip_vecchia_vif_get_point_terms(12) needs gpb_hip_vecchia_vif_grad_sums as the last full-scale Vecchia call"); }
+  else return fail("gpb_hip_vecchia_vif_get_point_terms: nterms = %d (3 after vif_factor, 12 after vif_grad_sums)", nterms);
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  HIP_OK(hipMemcpy(out_host, h->d_vif_part, sizeof(double) * (size_t)nterms * h->n, hipMemcpyDeviceToHost));
   API_END();
 }
 

@@ -965,7 +965,7 @@ int vif_lap_factor(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double v
   if (vif_resid_factor(h, 0, Li.data(), cov_type, var, a, true, with_grad ? h->d_vdC : nullptr)) return -1;
   HIP_OK(gpb::launch_reduce_partials(h->d_vif_part, n, 3, h->d_vout, nullptr, st, nullptr));
   HIP_OK(gpb::launch_vif_spmm(h->d_A, h->d_nn, 0, n, h->m, kq, h->d_vC, h->d_vQ, with_grad ? h->d_vdC : nullptr, with_grad ? h->d_vQdC : nullptr, st));
-  HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, kq, h->d_vgpart, h->d_vG, st));
+  HIP_OK(gpb::launch_vif_gram(h->d_vQ, h->d_D, n, k, kq, h->d_vgpart, h->d_vG, st));
   double o[3];
   std::vector<double> G((size_t)kq * kq);
   HIP_OK(hipMemcpyAsync(o, h->d_vout, sizeof(double) * 3, hipMemcpyDeviceToHost, st));

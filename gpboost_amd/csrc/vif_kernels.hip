@@ -578,21 +578,25 @@ __global__ __launch_bounds__(256) void vif_gram_kernel(const double* __restrict_
 #pragma unroll
     for (int c = 0; c < 4; ++c) out[(tr + 16 * r) * 64 + tc + 16 * c] = acc[r][c];
 }
-// G[a][b] = G[b][a] = sum over the chunks (ascending) of the tile entries; G: [kq][kq] row-major
-__global__ __launch_bounds__(256) void vif_gram_sum_kernel(const double* __restrict__ part, int nchunks, int nt, int kq, double* __restrict__ G) {
+// G[a][b] = G[b][a] = sum over the chunks (ascending) of the tile entries; G: [kq][kq] row-major.
+// A diagonal tile holds (a, b) and (b, a) as two sums that differ in the side the division by D entered (fl(Q_a / D) Q_b against fl(Q_b / D) Q_a): one rounding
+// apart.  G is symmetric exactly: one of the two serves both entries -- the one the host has always read: below the diagonal inside the k x k block (the
+// Woodbury matrix is factorised from its lower triangle), and for the response (row / column k) the entry (b, k) of its column, (B C)' D^-1 u with the
+// cross-covariance scaled.
+__global__ __launch_bounds__(256) void vif_gram_sum_kernel(const double* __restrict__ part, int nchunks, int nt, int k, int kq, double* __restrict__ G) {
   const int pair = blockIdx.x;
   int t = pair, ti = 0;
   while (t >= ti + 1) { t -= ti + 1; ++ti; }
   const int tj = t;
   const int npairs = nt * (nt + 1) / 2;
   for (int e = threadIdx.x; e < 4096; e += 256) {
-    double s = 0.0;
-    for (int c = 0; c < nchunks; ++c) s += part[((size_t)c * npairs + pair) * 4096 + e];
     const int a = ti * 64 + (e >> 6), b = tj * 64 + (e & 63);
-    if (a < kq && b < kq) {
-      G[(size_t)a * kq + b] = s;
-      if (ti != tj) G[(size_t)b * kq + a] = s;
-    }
+    if (a >= kq || b >= kq || (ti == tj && a < b)) continue;
+    const int src = (ti == tj && a == k) ? (((e & 63) << 6) | (e >> 6)) : e;      // row k of a diagonal tile: the transposed entry (b, k)
+    double s = 0.0;
+    for (int c = 0; c < nchunks; ++c) s += part[((size_t)c * npairs + pair) * 4096 + src];
+    G[(size_t)a * kq + b] = s;
+    if (a != b) G[(size_t)b * kq + a] = s;
   }
 }
 
@@ -830,11 +834,11 @@ size_t vif_gram_part_doubles(int n, int kq) {
   const int nt = (kq + 63) / 64;
   return (size_t)vif_gram_chunks(n, kq) * (nt * (nt + 1) / 2) * 4096;
 }
-hipError_t launch_vif_gram(const double* Q, const double* D, int n, int kq, double* part, double* G, hipStream_t st) {
+hipError_t launch_vif_gram(const double* Q, const double* D, int n, int k, int kq, double* part, double* G, hipStream_t st) {
   const int nt = (kq + 63) / 64, pairs = nt * (nt + 1) / 2, chunks = vif_gram_chunks(n, kq);
   const int rpc = (((n + chunks - 1) / chunks) + 15) / 16 * 16;
   hipLaunchKernelGGL(vif_gram_kernel, dim3(pairs, chunks), dim3(256), 0, st, Q, D, n, kq, nt, rpc, part);
-  hipLaunchKernelGGL(vif_gram_sum_kernel, dim3(pairs), dim3(256), 0, st, part, chunks, nt, kq, G);
+  hipLaunchKernelGGL(vif_gram_sum_kernel, dim3(pairs), dim3(256), 0, st, part, chunks, nt, k, kq, G);
   return hipGetLastError();
 }
 hipError_t launch_vif_vec(const double* Q, const double* C, const double* D, const double* w, int n, int k, int kq, double* v, double* z, hipStream_t st) {
@@ -842,6 +846,13 @@ hipError_t launch_vif_vec(const double* Q, const double* C, const double* D, con
   return hipGetLastError();
 }
 static int vif_tiles(int m) { return m <= 62 ? (m + 1 + 15) / 16 : 0; }      // NT of the per-point kernels: 1..4 (one wavefront, MFMA Gram) or 0
+// The largest dynamic LDS a per-point kernel may ask for: the 160 KiB of a workgroup minus the STATIC arrays of the larger kernel, the derivative kernel at
+// T = 128 (six T-vectors, s_pk and s_pk2 [4][T], s_self, s_idx, one double4).  A flat 150 KiB let m = 107 and 108 through, whose derivative launch then failed
+// with "invalid argument" (151728 + 14912 bytes); with this limit they are refused by name when the inducing points are set.
+size_t vif_resid_lds_max() {
+  constexpr size_t kStaticGrad = sizeof(double) * (6 * 128 + 2 * 4 * 128 + 4) + sizeof(int) * 128 + sizeof(double4);
+  return 160 * 1024 - kStaticGrad;
+}
 size_t vif_resid_lds_bytes(int m, int kq_grad) {      // kq_grad > 0: the derivative kernel (its five k-vectors alias the chunk buffer)
   const size_t chunk = (size_t)vif_staged_rows(m, vif_tiles(m)) * kVifKCP, vecs = 5 * (size_t)kq_grad;
   return sizeof(double) * ((size_t)(m + 1) * ((m + 1) | 1) + (chunk > vecs ? chunk : vecs));
@@ -851,7 +862,7 @@ hipError_t launch_vif_resid_factor(int cov, const VecchiaKernelArgs& args, const
   if (npts <= 0 || args.m < 1 || args.m > GPB_MAX_NEIGHBORS_BIG) return hipErrorInvalidValue;
   const int ld = (args.m + 1) | 1;
   const size_t lds = vif_resid_lds_bytes(args.m, 0);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (lds > vif_resid_lds_max()) return hipErrorInvalidValue;
 #define GPB_VIF_LAUNCH_T(C_, T_, NT_)                                                                                                   \
   do {                                                                                                                              \
     auto kern = vif_resid_factor_kernel<C_, T_, NT_>;                                                                                   \
@@ -884,7 +895,7 @@ hipError_t launch_vif_resid_grad(int cov, const VecchiaKernelArgs& args, const V
   if (npts <= 0 || args.m < 1 || args.m > GPB_MAX_NEIGHBORS_BIG) return hipErrorInvalidValue;
   const int ld = (args.m + 1) | 1;
   const size_t lds = vif_resid_lds_bytes(args.m, kq);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (lds > vif_resid_lds_max()) return hipErrorInvalidValue;
   VifGradArgs g;
   g.V = L.V; g.C = L.C; g.dC = L.dC; g.Q = L.Q; g.QdC = L.QdC; g.X1 = L.X1; g.V1 = L.V1; g.X2r = L.X2r; g.Hm = L.Hm; g.w = L.w; g.v = L.v; g.z = L.z;
   g.dA0 = L.dA0; g.dA1 = L.dA1; g.dD0 = L.dD0; g.dD1 = L.dD1; g.partials = L.partials; g.kip = kip; g.kq = kq; g.kp = 0; g.ld = ld;

@@ -252,6 +252,48 @@ class VecchiaState(object):
         Sigma = C Sigma_m^-1 C' + the Vecchia approximation of the residual process."""
         ipf = np.asfortranarray(ip, dtype=np.float64)
         _shim_call(_lib().gpb_hip_vecchia_vif_set_inducing_points(self.h, C.c_int(ipf.shape[0]), _p(ipf)))
+        self._vif_k = ipf.shape[0]
+
+    def _vif_kq(self):
+        return (self._vif_k + 1 + 7) // 8 * 8
+
+    def vif_factor(self, cov_type, var, a, Linv, with_grad=False):
+        """gpb_hip_vecchia_vif_factor -> (out3 = {sum u^2 / D, sum log D, #(D <= 0)}, G (k + 1) x (k + 1)); Linv: k x k inverse Cholesky factor of Sigma_m."""
+        Linv = np.ascontiguousarray(Linv, dtype=np.float64)
+        k = Linv.shape[0]
+        out3 = np.empty(3); G = np.empty((k + 1, k + 1))
+        _shim_call(_lib().gpb_hip_vecchia_vif_factor(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(Linv), C.c_int(1 if with_grad else 0), _p(out3), _p(G)))
+        return out3, G
+
+    def vif_grad_sums(self, cov_type, var, a, Winv, Si, N0, negMp1, w, keep_factor=False):
+        """gpb_hip_vecchia_vif_grad_sums -> sums12 in the order [2 * S + p]; the four matrices k x k (symmetric), w: k."""
+        mats = [np.ascontiguousarray(M, dtype=np.float64) for M in (Winv, Si, N0, negMp1)]
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        out = np.empty(12)
+        _shim_call(_lib().gpb_hip_vecchia_vif_grad_sums(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(mats[0]), _p(mats[1]), _p(mats[2]), _p(mats[3]),
+                                                        _p(w), C.c_int(1 if keep_factor else 0), _p(out)))
+        return out
+
+    def vif_get_grad_factor(self, p):
+        """dA (n x m), dD (n) of parameter p of the last vif_grad_sums(keep_factor = True)"""
+        dA = np.empty((self.n, self.m)); dD = np.empty(self.n)
+        _shim_call(_lib().gpb_hip_vecchia_vif_get_grad_factor(self.h, C.c_int(int(p)), _p(dA), _p(dD)))
+        return dA, dD
+
+    VIF_MATRICES = {"C": 0, "dC": 1, "V": 2, "Q": 3, "QdC": 4, "Hm": 5, "X1": 6, "V1": 7, "X2r": 8, "v": 9, "z": 10, "G": 11}      # GPB_VIF_MAT_* (include/gpb_hip.h)
+
+    def vif_get_matrix(self, which):
+        """Test seam (gpb_hip_vecchia_vif_get_matrix): a copy of one device buffer of the last vif_factor / vif_grad_sums: n x kq, or n (v, z), or kq x kq (G)."""
+        kq = self._vif_kq()
+        out = np.empty(self.n if which in ("v", "z") else ((kq, kq) if which == "G" else (self.n, kq)))
+        _shim_call(_lib().gpb_hip_vecchia_vif_get_matrix(self.h, C.c_int(self.VIF_MATRICES[which]), _p(out)))
+        return out
+
+    def vif_get_point_terms(self, nterms):
+        """Test seam (gpb_hip_vecchia_vif_get_point_terms): the per-point partials [nterms][n], 3 after vif_factor, 12 after vif_grad_sums."""
+        out = np.empty((int(nterms), self.n))
+        _shim_call(_lib().gpb_hip_vecchia_vif_get_point_terms(self.h, C.c_int(int(nterms)), _p(out)))
+        return out
 
     def laplace_set_inducing_points(self, ip):
         """Inducing points (k x d) of the "fitc" preconditioner (gpb_hip_vecchia_laplace_set_inducing_points)."""

@@ -202,6 +202,14 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_vif_factor(gpb_hip_vecchia_t* h, int cov_type
 GPB_HIP_EXPORT int gpb_hip_vecchia_vif_grad_sums(gpb_hip_vecchia_t* h, int cov_type, double var, double a, const double* Winv, const double* Si,
                                                  const double* N0, const double* negMp1, const double* w_host, int keep_factor, double* sums12_host);
 GPB_HIP_EXPORT int gpb_hip_vecchia_vif_get_grad_factor(gpb_hip_vecchia_t* h, int p, double* dA_host, double* dD_host);
+/* Read-only test seam (tests/test_zz_vif_kernels_gpu.py): copies of the device buffers of the last vif_factor / vif_grad_sums after a stream synchronisation; no kernel
+ * is launched.  which = GPB_VIF_MAT_*: C, V, Q (after vif_factor), dC, QdC (after vif_factor(with_grad = 1)), Hm, X1, V1, X2r (after vif_grad_sums) as n x kq row-major,
+ * kq = k + 1 rounded up to a multiple of 8; v, z (after vif_grad_sums): n; G: kq x kq.  A buffer the last call did not produce is an error that names the missing call.
+ * get_point_terms: the per-point partial sums [nterms][n]: 3 right after vif_factor ({log D_i, u_i^2 / D_i, [D_i <= 0]}), 12 right after vif_grad_sums ([2 s + p]). */
+enum { GPB_VIF_MAT_C = 0, GPB_VIF_MAT_DC = 1, GPB_VIF_MAT_V = 2, GPB_VIF_MAT_Q = 3, GPB_VIF_MAT_QDC = 4, GPB_VIF_MAT_HM = 5, GPB_VIF_MAT_X1 = 6, GPB_VIF_MAT_V1 = 7,
+       GPB_VIF_MAT_X2R = 8, GPB_VIF_MAT_VEC_V = 9, GPB_VIF_MAT_VEC_Z = 10, GPB_VIF_MAT_G = 11 };
+GPB_HIP_EXPORT int gpb_hip_vecchia_vif_get_matrix(gpb_hip_vecchia_t* h, int which, double* out_host);
+GPB_HIP_EXPORT int gpb_hip_vecchia_vif_get_point_terms(gpb_hip_vecchia_t* h, int nterms, double* out_host);
 
 /* Route B seam switch: thread-local flag the reference's patched find_nearest_neighbors_Vecchia_fast consults -- set by
  * REModelTemplate's constructor around CreateREComponentsVecchia when GPU_use was requested, so that the ordered neighbour search of model creation
