@@ -23,6 +23,7 @@ struct LaplaceState {
     gpb::LapEnt* hent = nullptr; gpb::LapEnt* oent = nullptr;
     gpb::LapEnt* hent_g = nullptr; gpb::LapEnt* oent_g = nullptr;      // the same layout with the entries of dA / d log(range) (gradient only)
     int nlev = 0, nslots = 0; size_t novf = 0;
+    int npad = 0, nmulti = 0, nlong = 0;      // padding slots, rows of several slots, slots of more than 64 entries (what the schedule holds: gpb_hip_vecchia_laplace_ops_check)
     std::vector<int> ptr_host;      // host copy of ptr (slot range of a run of levels: the barrier-free solves)
     // dense block of the solve (laplace_kernels.h: LapDense): K rows, device arrays, host level boundaries
     int dK = 0; int* d_rows = nullptr; int* d_iptr = nullptr; int* d_icol = nullptr; int* d_ipos = nullptr;
@@ -208,6 +209,7 @@ int upload_tri(int n, const std::vector<int>& lev, int nlev, const std::vector<i
     for (int l = 32; l < cnt; ++l) { osrc.push_back(sigma[src[l]]); opos.push_back(pos[l]); }
     optr.push_back((int)osrc.size());
   };
+  t->npad = t->nmulti = t->nlong = 0;
   for (int l = 0; l < nlev; ++l) {
     ptr[l] = (int)rows.size();
     for (int k = lptr[l]; k < lptr[l + 1]; ++k) {
@@ -218,9 +220,11 @@ int upload_tri(int n, const std::vector<int>& lev, int nlev, const std::vector<i
       if (ns > 1) lsplit[l] = 1;
       const int per = (len + ns - 1) / ns;                    // entries per slot (<= 64 unless len > 64 * 64)
       const int in_round = ((int)rows.size() - ptr[l]) % RR;
-      if (in_round + ns > RR) for (int z = in_round; z < RR; ++z) push_slot(-1, 0, nullptr, nullptr, 0);
+      if (in_round + ns > RR) for (int z = in_round; z < RR; ++z) { push_slot(-1, 0, nullptr, nullptr, 0); t->npad++; }
+      if (ns > 1) t->nmulti++;
       for (int sgi = 0; sgi < ns; ++sgi) {
         const int lo = std::min(len, sgi * per), hi = std::min(len, lo + per);
+        if (hi - lo > 64) t->nlong++;
         push_slot(sgi == 0 ? sigma[i] : -1, sgi == 0 ? ns : 0, e_src.data() + e_ptr[i] + lo, e_pos.data() + e_ptr[i] + lo, hi - lo);
       }
     }
@@ -697,6 +701,132 @@ int gpb_hip_lowrank_ops_check(int32_t op, int32_t n, int32_t k, int32_t ncol, in
   else HIP_OK(gpb::pc_combine(d_L, d_W, in_place ? res : d_X, d_x2, n, k, ncol, nc, mode, res, nullptr));
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemcpy(out, d_out, sizeof(double) * (nout + 2 * (size_t)guard), hipMemcpyDeviceToHost));
+  API_END();
+}
+
+// Test entry (include/gpb_hip.h): one launcher of the sparse Vecchia-Laplace machinery on the caller's A / D / W, with the handle's schedules (build_levels) and a chosen
+// solver form.  Entry records, dense inverses, vectors, scratch and the error word are this call's own; the operands travel in Vecchia order as plain columns and are
+// scattered here into storage order and the [chunk][row][nc] layout.  The output and every scratch vector start as `prefill`.
+int gpb_hip_vecchia_laplace_ops_check(gpb_hip_vecchia_t* h, int32_t op, int32_t form, int32_t ncol, int32_t nc, int32_t prefill, const double* A, const double* D,
+                                      const double* W, const double* scale, const double* A2, const double* X, double* out, double* out2, int32_t* info) {
+  API_BEGIN();
+  if (!h || !A || !X || !out || !info) return fail("gpb_hip_vecchia_laplace_ops_check: null argument");
+  if (op < 0 || op > 6 || (form != 0 && form != 1 && form != 4) || ncol < 1 || (nc != 1 && nc != 4) || prefill < 0 || prefill > 3)
+    return fail("gpb_hip_vecchia_laplace_ops_check: invalid argument (op 0..6, form 0 / 1 / 4, ncol >= 1, nc 1 or 4, prefill 0..3)");
+  if ((op == 2 && (!D || !W)) || ((op == 3 || op == 4) && !scale) || (op >= 5 && !A2) || ((op == 2 || op == 3) && !out2))
+    return fail("gpb_hip_vecchia_laplace_ops_check: null operand");
+  HIP_OK(hipSetDevice(h->device));
+  if (!h->has_nn) return fail("gpb_hip_vecchia_laplace_ops_check: the handle has no neighbour table");
+  if (!h->lap) h->lap = new LaplaceState();
+  LaplaceState* s = h->lap;
+  if (!h->has_transpose && build_transpose(h)) return -1;
+  if (!h->has_levels && build_levels(h, s)) return -1;
+  const int n = h->n, m = h->m;
+  hipStream_t st = h->stream;
+  const size_t nblk = (size_t)ncol * nc * n;
+  static const unsigned long long kFill[4] = { 0ull, 0x7FF8000000000000ull, 0x7FF0000000000000ull, gpb::kLapEmpty };
+  double fillv;
+  std::memcpy(&fillv, &kFill[prefill], sizeof(double));
+  std::vector<double> stage;
+  const auto filled = [&](DevBuf<double>& b, size_t cnt) -> hipError_t {
+    stage.assign(cnt, fillv);
+    hipError_t e = b.alloc(cnt);
+    return e != hipSuccess ? e : hipMemcpy(b, stage.data(), sizeof(double) * cnt, hipMemcpyHostToDevice);
+  };
+  const auto per_row = [&](DevBuf<double>& b, const double* src) -> hipError_t {      // Vecchia order -> storage order
+    stage.resize(n);
+    for (int i = 0; i < n; ++i) stage[s->sigma[i]] = src[i];
+    hipError_t e = b.alloc(n);
+    return e != hipSuccess ? e : hipMemcpy(b, stage.data(), sizeof(double) * n, hipMemcpyHostToDevice);
+  };
+  DevBuf<double> dA, dA2, dD, dW, dS, dX, dOut, dOut2, dinv[2], dtbuf[2];
+  DevBuf<gpb::LapEnt> hent[2], oent[2], hent_g[2], oent_g[2];
+  DevBuf<int> derr;
+  HIP_OK(dA.alloc((size_t)n * m));
+  HIP_OK(hipMemcpy(dA, A, sizeof(double) * (size_t)n * m, hipMemcpyHostToDevice));
+  if (D) HIP_OK(per_row(dD, D));
+  if (W) HIP_OK(per_row(dW, W));
+  if (scale) HIP_OK(per_row(dS, scale));
+  stage.resize(nblk);
+  for (int c = 0; c < ncol * nc; ++c) {
+    double* dst = stage.data() + (size_t)(c / nc) * n * nc + (size_t)(c % nc);
+    for (int i = 0; i < n; ++i) dst[(size_t)s->sigma[i] * nc] = X[(size_t)c * n + i];
+  }
+  HIP_OK(dX.alloc(nblk));
+  HIP_OK(hipMemcpy(dX, stage.data(), sizeof(double) * nblk, hipMemcpyHostToDevice));
+  HIP_OK(filled(dOut, nblk));
+  if (op == 2 || op == 3) HIP_OK(filled(dOut2, nblk));
+  HIP_OK(derr.alloc(1));
+  HIP_OK(hipMemset(derr, 0, sizeof(int)));
+  gpb::LapLevels lv = make_levels(h, s);
+  lv.A = dA; lv.syncfree = form; lv.err = derr;
+  LaplaceState::Tri* tris[2] = { &s->fwd, &s->bwd };
+  gpb::LapTri* lts[2] = { &lv.fwd, &lv.bwd };
+  gpb::LapDense* lds[2] = { &lv.fdense, &lv.bdense };
+  for (int q = 0; q < 2; ++q) {
+    const LaplaceState::Tri* tr = tris[q];
+    const size_t nh = (size_t)tr->nslots * 32, no = std::max<size_t>(tr->novf, 1);
+    HIP_OK(hent[q].alloc(nh)); HIP_OK(oent[q].alloc(no));
+    const bool dense = tr->dK > 0 && (op == 3 || op == 4);
+    if (dense) {
+      HIP_OK(filled(dinv[q], (size_t)tr->dK * tr->dK));
+      HIP_OK(filled(dtbuf[q], (size_t)tr->dK * gpb::kDenseCols * (1 + gpb::kDenseSplit)));
+      lds[q]->inv = dinv[q]; lds[q]->tbuf = dtbuf[q];
+    }
+    // everything from here on is ordered by the handle's stream (a non-blocking one: the synchronous copies above are not ordered against it by themselves)
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpyAsync(hent[q], tr->hent, sizeof(gpb::LapEnt) * nh, hipMemcpyDeviceToDevice, st));      // the sources; the coefficients are refreshed below
+    HIP_OK(hipMemcpyAsync(oent[q], tr->oent, sizeof(gpb::LapEnt) * no, hipMemcpyDeviceToDevice, st));
+    HIP_OK(gpb::lap_permute_factor(dA, tr->hpos, tr->opos, nh, tr->novf, hent[q], oent[q], st));
+    lts[q]->hent = hent[q]; lts[q]->oent = oent[q];
+    if (dense) HIP_OK(gpb::lap_dense_build(*lds[q], dA, st));
+  }
+  gpb::LapTri tg = op == 6 ? lv.bwd : lv.fwd;
+  if (op >= 5) {      // the same layout with a second coefficient array, as the gradient holds dA / d log(range)
+    const int q = op - 5;
+    const LaplaceState::Tri* tr = tris[q];
+    const size_t nh = (size_t)tr->nslots * 32, no = std::max<size_t>(tr->novf, 1);
+    HIP_OK(dA2.alloc((size_t)n * m));
+    HIP_OK(hipMemcpy(dA2, A2, sizeof(double) * (size_t)n * m, hipMemcpyHostToDevice));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hent_g[q].alloc(nh)); HIP_OK(oent_g[q].alloc(no));
+    HIP_OK(hipMemcpyAsync(hent_g[q], hent[q], sizeof(gpb::LapEnt) * nh, hipMemcpyDeviceToDevice, st));
+    HIP_OK(hipMemcpyAsync(oent_g[q], oent[q], sizeof(gpb::LapEnt) * no, hipMemcpyDeviceToDevice, st));
+    HIP_OK(gpb::lap_permute_factor(dA2, tr->hpos, tr->opos, nh, tr->novf, hent_g[q], oent_g[q], st));
+    tg.hent = hent_g[q]; tg.oent = oent_g[q];
+  }
+  switch (op) {
+    case 0: HIP_OK(gpb::lap_B(lv, n, dX, dOut, ncol, nc, st)); break;
+    case 1: HIP_OK(gpb::lap_Bt(lv, n, dX, dOut, ncol, nc, st)); break;
+    case 2: HIP_OK(gpb::lap_apply(lv, n, dD, dW, dX, dOut, dOut2, ncol, nc, st)); break;
+    case 3: HIP_OK(gpb::lap_vadu(lv, n, dS, dX, dOut, dOut2, ncol, nc, st)); break;
+    case 4: HIP_OK(gpb::lap_fwd_solve(lv, n, dS, dX, dOut, ncol, nc, st)); break;
+    default: HIP_OK(gpb::lap_mul(tg, n, dX, dOut, ncol, nc, st)); break;
+  }
+  HIP_OK(hipStreamSynchronize(st));
+  int err = 0;
+  HIP_OK(hipMemcpy(&err, derr, sizeof(int), hipMemcpyDeviceToHost));
+  const auto fetch = [&](const DevBuf<double>& b, double* dst) -> hipError_t {      // storage order, [chunk][row][nc] -> plain columns in Vecchia order
+    hipError_t e = hipMemcpy(stage.data(), b, sizeof(double) * nblk, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (int c = 0; c < ncol * nc; ++c) {
+      const double* src = stage.data() + (size_t)(c / nc) * n * nc + (size_t)(c % nc);
+      for (int i = 0; i < n; ++i) dst[(size_t)c * n + i] = src[(size_t)s->sigma[i] * nc];
+    }
+    return hipSuccess;
+  };
+  stage.resize(nblk);
+  HIP_OK(fetch(dOut, out));
+  if (op == 2 || op == 3) HIP_OK(fetch(dOut2, out2));
+  std::memset(info, 0, sizeof(int32_t) * 24);
+  for (int q = 0; q < 2; ++q) {
+    const LaplaceState::Tri* tr = tris[q];
+    int nwide = 0, nrun = 0;
+    for (const gpb::LapSeg& sg : (q == 0 ? s->fseg : s->bseg)) { if (sg.nsplit > 1) ++nwide; else ++nrun; }
+    const int32_t f[9] = { tr->nlev, tr->nslots, (int32_t)tr->novf, tr->dK, nwide, nrun, tr->npad, tr->nmulti, tr->nlong };
+    std::memcpy(info + 9 * q, f, sizeof(f));
+  }
+  info[18] = err; info[19] = gpb::lap_sf_resident(); info[20] = gpb::lap_sfw_resident();
   API_END();
 }
 
@@ -1445,7 +1575,7 @@ int lap_eval_workspace(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs&
   const int n = h->n, t = e.t;
   const LapWork w = lap_work(h, s, t);                 // (its sizes; the views are taken once everything is allocated)
   const int tc = w.tc, p_max = std::min(e.cg_max_num_it_tridiag, n);
-  if (!s->d_vec) {      // zero-initialised: padding entries of the solves multiply 0 with whatever sits in x[0]
+  if (!s->d_vec) {      // zero-initialised (the solves themselves select padding entries out: their results do not depend on what a vector held before)
     HIP_OK(hipMalloc(&s->d_vec, LapWork::vec_bytes(n)));
     HIP_OK(hipMemset(s->d_vec, 0, LapWork::vec_bytes(n)));
   }

@@ -40,7 +40,7 @@ struct LapLevels {                        // fwd: (D^-1 + W) B z = t;  bwd: B^T 
   LapDense fdense, bdense;                // head block of the forward solve (before fseg), tail block of the backward solve (after bseg)
   const double* A;                        // this evaluation's coefficients, Vecchia order [n][m] (the blocks' entries point into it)
   // barrier-free solves (lap_sptrsv_sf_kernel): one launch per triangular solve for all levels of fseg / bseg
-  int syncfree = 0;                       // 1: use them
+  int syncfree = 0;                       // bit mask: 1 = single vectors (nc == 1), 4 = the probe block (nc == 4); 0 = one launch per level
   const int* fwd_ptr_host = nullptr;      // HOST copies of fwd.ptr / bwd.ptr (slot range of a run of levels)
   const int* bwd_ptr_host = nullptr;
   int* err = nullptr;                     // device word: set when a bounded spin ran out (a dependency never arrived)
@@ -49,6 +49,11 @@ struct CgScalars {         // per-column CG scalars on the device; part / part2:
   double* a; double* a_old; double* b; double* rz_old; double* rnorm; double* Td; double* Ts; double* part; double* part2;
 };
 int lap_cg_parts(int n);
+// the value a barrier-free solve pre-sets its rows to (a NaN pattern no arithmetic produces), and the workgroups its launchers hold to be resident at
+// once: lap_sptrsv_sf_kernel (single vectors), lap_sptrsv_sfw_kernel (probe block)
+constexpr unsigned long long kLapEmpty = 0xFFF8DEAD0000BEEFull;
+int lap_sf_resident();
+int lap_sfw_resident();
 
 // the response as the likelihood kernels see it: int labels / counts (yi), or real values (yd: the likelihoods with a real-valued response, and
 // proportions under the logit / probit links; lik_table.h says which likelihood reads which), and the likelihood's auxiliary parameters

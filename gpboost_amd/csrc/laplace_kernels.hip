@@ -503,7 +503,9 @@ __global__ __launch_bounds__(kTriThreads) void lap_sptrsv_kernel(LapTri T, const
     // (2) ... then the prefetches of the next two rounds (independent of x)
     issueA(NS, dnn, ann);
     issueB(NS, dn, an, bn);
-    // (3) slot sums; padding entries: coefficient 0 times a finite x (the workspace is zero-initialised)
+    // (3) slot sums; an entry with coefficient 0 (padding, a masked overflow entry) is not a dependency: it is selected out, so that it adds exactly
+    // nothing whatever its source holds -- after a barrier-free solve has given up, x still carries the pending-row NaN pattern at the abandoned rows,
+    // and 0 x NaN would spread it (the barrier-free kernels skip such entries in the same way)
 #pragma unroll
     for (int s = 0; s < ns; ++s) {
       double sum[NC];
@@ -513,8 +515,8 @@ __global__ __launch_bounds__(kTriThreads) void lap_sptrsv_kernel(LapTri T, const
       for (int k = 0; k < 2; ++k) {
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          sum[c] = __builtin_fma(b.ha[s][k], g[s][k].v[c], sum[c]);
-          if (OVF) sum[c] = __builtin_fma(b.oa[s][k], g[s][2 + k].v[c], sum[c]);
+          sum[c] = b.ha[s][k] != 0.0 ? __builtin_fma(b.ha[s][k], g[s][k].v[c], sum[c]) : sum[c];
+          if (OVF) sum[c] = b.oa[s][k] != 0.0 ? __builtin_fma(b.oa[s][k], g[s][2 + k].v[c], sum[c]) : sum[c];
         }
       }
       // slots longer than 64 entries exist only when a row has > 4096 entries
@@ -527,7 +529,7 @@ __global__ __launch_bounds__(kTriThreads) void lap_sptrsv_kernel(LapTri T, const
           if (!in) o.val = 0.0;
           const VecN<NC> gg = ldvec<NC, LS>((const double*)xc, (unsigned)o.src);
 #pragma unroll
-          for (int c = 0; c < NC; ++c) sum[c] = __builtin_fma(o.val, gg.v[c], sum[c]);
+          for (int c = 0; c < NC; ++c) sum[c] = o.val != 0.0 ? __builtin_fma(o.val, gg.v[c], sum[c]) : sum[c];
         }
       }
 #pragma unroll
@@ -1285,7 +1287,6 @@ hipError_t lap_objective(int link, const double* x, const LikResp& y, const doub
 // and the row is given up): a mistake must not hang the device.
 // Arithmetic: per slot the same fma order and the same 16-lane butterfly as lap_sptrsv_kernel, slot sums of a split row added in
 // slot order -- results are bit-identical to the level-scheduled solve.
-constexpr unsigned long long kLapEmpty = 0xFFF8DEAD0000BEEFull;
 constexpr int kLapSpinLimit = 1 << 20;
 constexpr int kSfThreads = 256;
 
@@ -1680,14 +1681,9 @@ static void lap_dense_solve(const LapDense& d, const double* A, int n, const dou
     }
   }
 }
-// one launch (+ the sentinel prefill) for all levels of the segments [seg[0].L0, seg[nseg-1].L1); ncol column units (nc == 4: chunks)
-template <bool SCALE>
-static hipError_t lap_trsv_syncfree(const LapTri& T, const int* host_ptr, const LapSeg* seg, int nseg, int n, const double* rhs, const double* rdw, double* x,
-                                    int ncol, int nc, int* err, hipStream_t st) {
-  if (nseg <= 0) return hipSuccess;
-  const int qa = host_ptr[seg[0].L0], qb = host_ptr[seg[nseg - 1].L1];
-  if (qb <= qa) return hipSuccess;
-  static int resident = 0;           // workgroups of 256 lanes the device holds at once (conservative: half of what the occupancy calculator admits)
+// workgroups of 256 lanes the device holds at once (conservative: half of what the occupancy calculator admits)
+int lap_sf_resident() {
+  static int resident = 0;
   if (resident == 0) {
     int occ = 0, cus = 0, dev = 0;
     (void)hipGetDevice(&dev);
@@ -1696,6 +1692,25 @@ static hipError_t lap_trsv_syncfree(const LapTri& T, const int* host_ptr, const 
     resident = std::max(1, occ * cus / 2);
     (void)hipGetLastError();
   }
+  return resident;
+}
+// the same for the probe block's kernel (J = 1): stay below what the calculator admits
+int lap_sfw_resident() {
+  int occ = 0, cus = 0, dev = 0;
+  (void)hipGetDevice(&dev);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, lap_sptrsv_sfw_kernel<true, true, 1>, kSfwThreads, 0) != hipSuccess || occ < 1) occ = 1;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 64;
+  (void)hipGetLastError();
+  return std::max(1, occ * cus * 3 / 4);
+}
+// one launch (+ the sentinel prefill) for all levels of the segments [seg[0].L0, seg[nseg-1].L1); ncol column units (nc == 4: chunks)
+template <bool SCALE>
+static hipError_t lap_trsv_syncfree(const LapTri& T, const int* host_ptr, const LapSeg* seg, int nseg, int n, const double* rhs, const double* rdw, double* x,
+                                    int ncol, int nc, int* err, hipStream_t st) {
+  if (nseg <= 0) return hipSuccess;
+  const int qa = host_ptr[seg[0].L0], qb = host_ptr[seg[nseg - 1].L1];
+  if (qb <= qa) return hipSuccess;
+  const int resident = lap_sf_resident();
   const int nslot = qb - qa;
   for (int c0 = 0; c0 < ncol; ) {       // column units per pass: all of them unless there are more than resident workgroups
     const int cn = std::min(ncol - c0, resident);
@@ -1720,12 +1735,12 @@ static hipError_t lap_trsv_syncfree_block_j(const LapTri& T, int n, int qa, int 
                                             hipStream_t st) {
   const int nslot = qb - qa;
   const int units = (ncol + 4 * J - 1) / (4 * J);
-  int occ = 0, cus = 0, dev = 0;
+  static_assert(J == 1, "lap_sfw_resident() is the figure of J = 1");
+  int cus = 0, dev = 0;
   (void)hipGetDevice(&dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, lap_sptrsv_sfw_kernel<true, true, J>, kSfwThreads, 0) != hipSuccess || occ < 1) occ = 1;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 64;
   (void)hipGetLastError();
-  const int resident = std::max(1, occ * cus * 3 / 4);   // every workgroup of the launch must be resident (forward progress): stay below what the calculator admits
+  const int resident = lap_sfw_resident();              // every workgroup of the launch must be resident (forward progress)
   int total = 2 * cus;                                   // (measured at config 4, profiles/r04_c_*: J = 1 with 512 workgroups 279 ms, 256: 295, 768 / 1024: 300)
   total = std::min(total, resident);
   const int per_unit = std::max(1, std::min(total / units, (nslot + kSfwThreads / 64 - 1) / (kSfwThreads / 64)));

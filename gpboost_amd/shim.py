@@ -407,6 +407,34 @@ class VecchiaState(object):
         _shim_call(_lib().gpb_hip_vecchia_laplace_range_deriv(self.h, C.c_int(cov_type), C.c_double(var), C.c_double(a), _p(dA), _p(dD)))
         return dA, dD
 
+    _LAP_OPS = {"B": 0, "Bt": 1, "apply": 2, "vadu": 3, "fwd_solve": 4, "mul_fwd": 5, "mul_bwd": 6}
+    _LAP_PREFILL = {"zeros": 0, "nan": 1, "inf": 2, "sentinel": 3}
+    _LAP_INFO = ("nlev", "nslots", "novf", "dense_K", "wide_segments", "run_segments", "padding_slots", "split_rows", "long_slots")
+
+    def laplace_ops_check(self, op, A, X, nc=1, form=0, prefill="zeros", D=None, W=None, scale=None, A2=None):
+        """One launcher of the sparse Vecchia-Laplace machinery on the caller's factor (gpb_hip_vecchia_laplace_ops_check; test seam).  A (n, m), D / W / scale (n)
+        and the columns X (n, ncol * nc) in Vecchia order; form 0 = one launch per level, 1 / 4 = barrier-free (single vectors / probe block); prefill: what the results
+        and the scratch hold before the launch.  -> (out, out2 or None, info): results (n, ncol * nc), out2 = D^-1 B X of "apply" / t of "vadu"; info: dict with "fwd" and
+        "bwd" (the schedule's counts, _LAP_INFO), "err" (error word of the solves), "resident" (single vectors, probe block)."""
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        A = f64(A); X = np.asarray(X, dtype=np.float64)
+        Dc, Wc, Sc, A2c = f64(D), f64(W), f64(scale), f64(A2)
+        assert A.shape == (self.n, self.m) and X.ndim == 2 and X.shape[0] == self.n and X.shape[1] % nc == 0, (A.shape, X.shape, nc)
+        Xc = np.ascontiguousarray(X.T)
+        out = np.empty_like(Xc)
+        opi = self._LAP_OPS[op]
+        out2 = np.empty_like(Xc) if opi in (2, 3) else None
+        info = np.zeros(24, dtype=np.int32)
+        for v in (D, W, scale):
+            assert v is None or np.shape(v) == (self.n,)
+        assert A2 is None or np.shape(A2) == A.shape
+        _shim_call(_lib().gpb_hip_vecchia_laplace_ops_check(self.h, C.c_int(opi), C.c_int(int(form)), C.c_int(X.shape[1] // nc), C.c_int(int(nc)),
+                                                            C.c_int(self._LAP_PREFILL[prefill]), _p(A), _p(Dc), _p(Wc), _p(Sc), _p(A2c), _p(Xc),
+                                                            _p(out), _p(out2), _p(info, C.c_int32)))
+        d = {"fwd": dict(zip(self._LAP_INFO, (int(v) for v in info[:9]))), "bwd": dict(zip(self._LAP_INFO, (int(v) for v in info[9:18]))),
+             "err": int(info[18]), "resident": (int(info[19]), int(info[20]))}
+        return out.T, (None if out2 is None else out2.T), d
+
     def yaux_partial_dev(self, w_dev_ptr):
         """This shard's contribution to y_aux as a full n-vector on the device (sum over ranks = y_aux)."""
         _shim_call(_lib().gpb_hip_vecchia_yaux_partial_dev(self.h, C.c_void_p(int(w_dev_ptr))))

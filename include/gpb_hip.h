@@ -540,6 +540,21 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_reset_mode_to_previous(gpb_hip_vecchi
 GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_grad_F_current(gpb_hip_vecchia_t* h, double* gradF_host);
 GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int cov_type, double var, double a, double* dA_host,
                                                        double* dD_host);
+/* Test entry: ONE launcher of the sparse Vecchia-Laplace machinery (the triangular solves of P^-1 = B^-1 (D^-1 + W)^-1 B^-T and the products with B, B', Sigma^-1 + W)
+ * on the caller's own factor, with the handle's level schedules (neighbour table: gpb_hip_vecchia_set_neighbors / _find_neighbors) and a chosen solver form.
+ * A [n][m] and D, W, scale [n] in Vecchia order; X and the results: ncol * nc plain columns of n values in Vecchia order (nc = 1 or 4: columns per chunk of the
+ * device layout [chunk][row][nc] the entry scatters them into, in storage order).
+ *   op 0  out = B X                  op 1  out = B' X            op 2  out = (B' D^-1 B + W) X, out2 = D^-1 B X
+ *   op 3  lap_vadu: out2 = t with B' t = X, out = z with B z = scale .* t (scale = 1 / (1 / D + W) in the model)
+ *   op 4  out = B^-1 (scale .* X)    op 5  out = A2 X            op 6  out = A2' X   (A2 [n][m]: a second coefficient array in the layouts of the two solves)
+ * form: 0 = one launch per level, 1 / 4 = the barrier-free solves for single vectors / the probe block (taken when nc is 1 / 4; otherwise as 0).
+ * prefill: what the results and every scratch vector hold before the launch: 0 zeros, 1 quiet NaN, 2 +Inf, 3 the bit pattern the barrier-free solves mark a pending row with.
+ * info [24]: for the forward solve, then the backward one: levels, slots, overflow entries, rows of the dense block, segments of one wide level, segments of a run
+ * of narrow levels, padding slots, rows of several slots, slots of more than 64 entries; [18] the error word of the solves after the call; [19], [20] the workgroups the
+ * barrier-free launchers hold to be resident (single vectors, probe block). */
+GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_ops_check(gpb_hip_vecchia_t* h, int32_t op, int32_t form, int32_t ncol, int32_t nc, int32_t prefill, const double* A,
+                                                     const double* D, const double* W, const double* scale, const double* A2, const double* X, double* out,
+                                                     double* out2, int32_t* info);
 
 /* ------------------------------------------------------------------------------------
  * Exact (dense) GP, Gaussian likelihood -- BASELINE config 1: replaces CalcSigmaComps / CalcZSigmaZt / CalcChol /
