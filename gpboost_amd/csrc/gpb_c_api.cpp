@@ -17,6 +17,7 @@
 #include "../../include/gpboost_c_api_subset.h"
 #include "../../include/gpb_hip.h"
 #include "gpb_optim.h"
+#include "gpb_smallmat.h"
 #include "lik_table.h"
 
 #include <algorithm>
@@ -148,18 +149,7 @@ struct REModelHip {
 
 // The host-pointer entry points permute n-vectors between data order and Vecchia order (gathers / scatters over 8 MB at n = 1e6:
 // latency-bound on one core, ~1 ms); a few threads bring that to a fraction of the H2D copy that follows.
-template <class F>
-void parallel_for(int n, F&& body) {
-  const int hw = (int)std::thread::hardware_concurrency();
-  const int nt = n < 200000 ? 1 : std::max(1, std::min(8, hw > 0 ? hw : 1));
-  if (nt == 1) { body(0, n); return; }
-  std::vector<std::thread> th;
-  th.reserve(nt - 1);
-  const int per = (n + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) th.emplace_back([&, t] { body(std::min(n, t * per), std::min(n, (t + 1) * per)); });
-  body(0, std::min(n, per));
-  for (auto& x : th) x.join();
-}
+using gpb_sm::parallel_for;
 
 bool near(double a, double b) { return std::fabs(a - b) < 1e-10 * std::max({1.0, std::fabs(a), std::fabs(b)}); }  // utils.h:55
 
@@ -533,13 +523,6 @@ int prediction_response(REModelHip* mdl, const double* y_data, const double* fe)
 
 double range_const(const REModelHip* mdl) { return mdl->cov_type == 0 ? 1. : (mdl->cov_type == 1 ? std::sqrt(3.) : std::sqrt(5.)); }
 
-// Matern covariance with shape 0.5 / 1.5 / 2.5 (cov_type 0 / 1 / 2) on the host at the scaled distance r = a |x - x'|: e = scale exp(-r) times the shape's
-// polynomial.  A caller that multiplies its variance in afterwards passes scale = 1, so every site rounds as it always did.
-double matern_host(int cov_type, double scale, double r) {
-  const double e = scale * std::exp(-r);
-  return cov_type == 0 ? e : (cov_type == 1 ? e * (1. + r) : e * (1. + r + r * r / 3.));
-}
-
 // REModelTemplate::FindInitCovPar (re_model_template.h:4849-4968) -> RECompGP::FindInitCovPar (re_comp.h:1249-1267) ->
 // CovFunction::FindInitCovPar (cov_fcts.h:1422-1683) for one Gaussian Matern GP.  The result is used as cov_pars_ directly, i.e. it
 // is on the TRANSFORMED scale: (var(y) / 2, 1, a) with a such that the correlation is ~0.05 at half the median distance.
@@ -628,21 +611,11 @@ int profile_out_coef(REModelHip* mdl, double ratio, double a) {
   if (gpb_hip_vecchia_factor(mdl->vh, mdl->cov_type, ratio, a, 1)) return shim_error();
   std::vector<double> G((size_t)q * q);
   if (gpb_hip_vecchia_gram(mdl->vh, G.data())) return shim_error();
-  // Cholesky of X' Psi^-1 X (Eigen's llt().solve)
+  // Cholesky of X' Psi^-1 X (Eigen's llt().solve), in place in the Gram matrix
+  if (!gpb_sm::cholesky_lower(G.data(), p, q)) return set_error("The matrix X' Psi^-1 X of the linear regression covariates is not positive definite (collinear covariates?)");
   std::vector<double> L((size_t)p * p, 0.), rhs(p);
-  for (int i = 0; i < p; ++i) {
-    for (int j = 0; j <= i; ++j) {
-      double sacc = G[(size_t)i * q + j];
-      for (int k = 0; k < j; ++k) sacc -= L[(size_t)i * p + k] * L[(size_t)j * p + k];
-      if (i == j) {
-        if (!(sacc > 0.)) return set_error("The matrix X' Psi^-1 X of the linear regression covariates is not positive definite (collinear covariates?)");
-        L[(size_t)i * p + i] = std::sqrt(sacc);
-      } else L[(size_t)i * p + j] = sacc / L[(size_t)j * p + j];
-    }
-    rhs[i] = G[(size_t)i * q + p];
-  }
-  for (int i = 0; i < p; ++i) { double v = rhs[i]; for (int k = 0; k < i; ++k) v -= L[(size_t)i * p + k] * rhs[k]; rhs[i] = v / L[(size_t)i * p + i]; }
-  for (int i = p - 1; i >= 0; --i) { double v = rhs[i]; for (int k = i + 1; k < p; ++k) v -= L[(size_t)k * p + i] * rhs[k]; rhs[i] = v / L[(size_t)i * p + i]; }
+  for (int i = 0; i < p; ++i) { for (int j = 0; j <= i; ++j) L[(size_t)i * p + j] = G[(size_t)i * q + j]; rhs[i] = G[(size_t)i * q + p]; }
+  gpb_sm::cholesky_solve(L.data(), p, p, rhs.data());
   mdl->beta = rhs;
   mdl->chol_XtPsiInvX = L;
   if (gpb_hip_vecchia_set_resid(mdl->vh, mdl->beta.data())) return shim_error();
@@ -675,20 +648,6 @@ int kmeans_plusplus(const std::vector<double>& x, int n, int d, int k, std::mt19
   return 0;
 }
 
-// lower Cholesky factor of the k x k row-major matrix M (in place, upper part zeroed); false if not positive definite
-bool cholesky_lower(std::vector<double>& M, int k) {
-  for (int i = 0; i < k; ++i) {
-    for (int j = 0; j <= i; ++j) {
-      double sacc = M[(size_t)i * k + j];
-      for (int q = 0; q < j; ++q) sacc -= M[(size_t)i * k + q] * M[(size_t)j * k + q];
-      if (i == j) { if (!(sacc > 0.)) return false; M[(size_t)i * k + i] = std::sqrt(sacc); }
-      else M[(size_t)i * k + j] = sacc / M[(size_t)j * k + j];
-    }
-    for (int j = i + 1; j < k; ++j) M[(size_t)i * k + j] = 0.;
-  }
-  return true;
-}
-
 // Full-scale Vecchia, Gaussian likelihood: y' Psi^-1 y and log|Psi| at (ratio, a) by the Woodbury identity with the residual-process
 // Vecchia factor on the device (CalcSigmaComps re_model_template.h:8151-8200, CalcCovFactorFITC_FSA :9646-9745, CalcYAux :9785-9806,
 // the log-determinant :2950-2966) and -- with_grad -- their derivatives wrt (log ratio, log a): the analytic gradient of
@@ -700,92 +659,43 @@ struct VifSolve { std::vector<double> Linv, Lw, v; };      // for the prediction
 typedef int (*vif_factor_fn)(void* ctx, const double* Linv, int with_grad, double* out3, double* G);
 typedef int (*vif_gsums_fn)(void* ctx, const double* Winv, const double* Si, const double* N0, const double* negMp1, const double* w, double* sums12);
 
-// C = A B for k x k row-major matrices
-void matmul_kk(const std::vector<double>& A, const std::vector<double>& B, int k, std::vector<double>* C) {
-  C->assign((size_t)k * k, 0.);
-  parallel_for(k, [&](int lo, int hi) {
-    for (int i = lo; i < hi; ++i)
-      for (int q = 0; q < k; ++q) {
-        const double aiq = A[(size_t)i * k + q];
-        if (aiq == 0.) continue;
-        for (int j = 0; j < k; ++j) (*C)[(size_t)i * k + j] += aiq * B[(size_t)q * k + j];
-      }
-  });
-}
-// inverse of a lower-triangular k x k row-major matrix (row-major lower-triangular result), column by column
-void tri_inverse_lower(const std::vector<double>& L, int k, std::vector<double>* Linv) {
-  Linv->assign((size_t)k * k, 0.);
-  for (int c = 0; c < k; ++c) {
-    (*Linv)[(size_t)c * k + c] = 1. / L[(size_t)c * k + c];
-    for (int i = c + 1; i < k; ++i) {
-      double sacc = 0.;
-      for (int q = c; q < i; ++q) sacc -= L[(size_t)i * k + q] * (*Linv)[(size_t)q * k + c];
-      (*Linv)[(size_t)i * k + c] = sacc / L[(size_t)i * k + i];
-    }
-  }
-}
-// (L L')^-1 = Linv' Linv from the lower-triangular inverse
-void spd_inverse_from_tri(const std::vector<double>& Linv, int k, std::vector<double>* inv) {
-  inv->assign((size_t)k * k, 0.);
-  parallel_for(k, [&](int lo, int hi) {
-    for (int i = lo; i < hi; ++i)
-      for (int j = 0; j <= i; ++j) {
-        double sacc = 0.;
-        for (int q = i; q < k; ++q) sacc += Linv[(size_t)q * k + i] * Linv[(size_t)q * k + j];      // rows q >= max(i, j) = i
-        (*inv)[(size_t)i * k + j] = sacc;
-      }
-  });
-  for (int i = 0; i < k; ++i) for (int j = i + 1; j < k; ++j) (*inv)[(size_t)i * k + j] = (*inv)[(size_t)j * k + i];
-}
-
 int vif_terms_core(int k, int d, const double* ip_colmajor, int cov_type, double ratio, double a, int with_grad, vif_factor_fn factor, vif_gsums_fn gsums,
                    void* ctx, double* t7, VifSolve* keep) {
-  std::vector<double> Sm0((size_t)k * k), dSm1;
-  if (with_grad) dSm1.assign((size_t)k * k, 0.);
-  for (int i = 0; i < k; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double s2 = 0.;
-      for (int c = 0; c < d; ++c) { const double t = ip_colmajor[(size_t)c * k + i] - ip_colmajor[(size_t)c * k + j]; s2 += t * t; }
-      const double r = a * std::sqrt(s2), e = ratio * std::exp(-r);
-      const double kv = matern_host(cov_type, ratio, r);
-      Sm0[(size_t)i * k + j] = Sm0[(size_t)j * k + i] = kv;
-      if (with_grad) {      // d/d log a (GradientRangeMaternShape0_5 / 1_5 / 2_5 with transf_scale, cov_fcts.h:2535-2554)
-        const double dk = cov_type == 0 ? -r * e : (cov_type == 1 ? -r * r * e : -r * r * (1. + r) * e / 3.);
-        dSm1[(size_t)i * k + j] = dSm1[(size_t)j * k + i] = dk;
-      }
-    }
+  namespace sm = gpb_sm;
+  const size_t kk = (size_t)k * k;
+  std::vector<double> Sm0(kk), dSm1(with_grad ? kk : 0);      // dSm1 = d / d log a
+  sm::ip_cov(ip_colmajor, k, d, sm::IpLayout::ColMajorKxD, sm::MaternForm::GaussianPaths, cov_type, ratio, a, Sm0.data(), with_grad ? dSm1.data() : nullptr);
   std::vector<double> Sm = Sm0;
-  for (int i = 0; i < k; ++i) Sm[(size_t)i * k + i] *= 1. + 1e-6;                   // JITTER_MULT_IP_FITC_FSA (utils.h:41): only what is FACTORISED carries it
-  std::vector<double> L = Sm;
-  if (!cholesky_lower(L, k)) return set_error("The covariance matrix of the inducing points is not positive definite");
-  std::vector<double> Linv;
-  tri_inverse_lower(L, k, &Linv);
+  for (int i = 0; i < k; ++i) Sm[(size_t)i * k + i] *= sm::JITTER_MULT_IP_FITC_FSA;      // only what is FACTORISED carries it
+  std::vector<double> L = Sm, Linv(kk);
+  double ldm = 0., ldw = 0.;
+  if (!sm::cholesky_lower(L.data(), k, k, &ldm)) return set_error("The covariance matrix of the inducing points is not positive definite");
+  sm::tri_inverse_lower(L.data(), k, k, Linv.data());
   double o3[3];
   const int q = k + 1;
   std::vector<double> G((size_t)q * q);
   if (factor(ctx, Linv.data(), with_grad, o3, G.data())) return -1;                // device: (B [C_nm, y])' D^-1 (B [C_nm, y]) and the factor's sums
   std::vector<double> W((size_t)k * k), r(k);
   for (int i = 0; i < k; ++i) { for (int j = 0; j < k; ++j) W[(size_t)i * k + j] = Sm[(size_t)i * k + j] + G[(size_t)i * q + j]; r[i] = G[(size_t)i * q + k]; }
-  if (!cholesky_lower(W, k)) return set_error("The Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
-  double ldm = 0., ldw = 0.;
-  for (int i = 0; i < k; ++i) { ldm += std::log(L[(size_t)i * k + i]); ldw += std::log(W[(size_t)i * k + i]); }
-  for (int i = 0; i < k; ++i) { double v = r[i]; for (int j = 0; j < i; ++j) v -= W[(size_t)i * k + j] * r[j]; r[i] = v / W[(size_t)i * k + i]; }   // L_W^-1 r
+  if (!sm::cholesky_lower(W.data(), k, k, &ldw)) return set_error("The Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
+  sm::zero_upper(W.data(), k, k);                                                  // (it is kept for the prediction)
+  sm::solve_lower(W.data(), k, k, r.data());                                       // L_W^-1 r
   double rr = 0.; for (int i = 0; i < k; ++i) rr += r[i] * r[i];
   std::vector<double> w = r;                                                       // w = L_W^-T (L_W^-1 r) = W^-1 (B C)' D^-1 B y
-  for (int i = k - 1; i >= 0; --i) { double v = w[i]; for (int j = i + 1; j < k; ++j) v -= W[(size_t)j * k + i] * w[j]; w[i] = v / W[(size_t)i * k + i]; }
+  sm::solve_lower_transposed(W.data(), k, k, w.data());
   if (keep) { keep->Linv = Linv; keep->Lw = W; keep->v = w; }
   t7[0] = o3[0] - rr;
   t7[1] = o3[1] - 2. * ldm + 2. * ldw;
   t7[2] = o3[2];
   if (!with_grad) return 0;
   // ---- gradient -------------------------------------------------------------------------------------------------------------------------
-  std::vector<double> LwInv, Winv, Si, T, Mp0, Mp1;
-  tri_inverse_lower(W, k, &LwInv);
-  spd_inverse_from_tri(LwInv, k, &Winv);
-  spd_inverse_from_tri(Linv, k, &Si);
-  matmul_kk(Si, Sm0, k, &T); matmul_kk(T, Si, k, &Mp0);                            // Si dSm^var Si   (dSm^var = the UN-jittered Sigma_m, as the reference's GetZSigmaZtGrad)
-  matmul_kk(Si, dSm1, k, &T); matmul_kk(T, Si, k, &Mp1);                           // Si dSm^range Si
-  std::vector<double> N0((size_t)k * k), negMp1((size_t)k * k);
+  std::vector<double> LwInv(kk), Winv(kk), Si(kk), T(kk), Mp0(kk), Mp1(kk);
+  sm::tri_inverse_lower(W.data(), k, k, LwInv.data());
+  sm::spd_inverse_from_tri(LwInv.data(), k, Winv.data());
+  sm::spd_inverse_from_tri(Linv.data(), k, Si.data());
+  sm::matmul(Si.data(), Sm0.data(), k, T.data()); sm::matmul(T.data(), Si.data(), k, Mp0.data());      // Si dSm^var Si   (dSm^var = the UN-jittered Sigma_m, as the reference's GetZSigmaZtGrad)
+  sm::matmul(Si.data(), dSm1.data(), k, T.data()); sm::matmul(T.data(), Si.data(), k, Mp1.data());     // Si dSm^range Si
+  std::vector<double> N0(kk), negMp1(kk);
   for (size_t e = 0; e < N0.size(); ++e) { N0[e] = 2. * Si[e] - Mp0[e]; negMp1[e] = -Mp1[e]; }
   double S[12];
   if (gsums(ctx, Winv.data(), Si.data(), N0.data(), negMp1.data(), w.data(), S)) return -1;
@@ -2274,17 +2184,9 @@ int GPB_GetCoef(REModelHandle handle, double* optim_coef, bool calc_std_dev) {
     const int p = mdl->p_cov;
     if (p >= mdl->n) { for (int j = 0; j < p; ++j) optim_coef[p + j] = std::numeric_limits<double>::quiet_NaN(); return 0; }
     const std::vector<double>& L = mdl->chol_XtPsiInvX;
-    std::vector<double> col(p);
-    for (int j = 0; j < p; ++j) {          // (L L')^-1_jj = || L^-1 e_j ||^2
-      double ss = 0.;
-      for (int i = j; i < p; ++i) {
-        double v = (i == j) ? 1. : 0.;
-        for (int k = j; k < i; ++k) v -= L[(size_t)i * p + k] * col[k];
-        col[i] = v / L[(size_t)i * p + i];
-        ss += col[i] * col[i];
-      }
-      optim_coef[p + j] = std::sqrt(mdl->cov_pars_tr[0] * ss);
-    }
+    std::vector<double> ss(p);
+    gpb_sm::inverse_diagonal(L.data(), p, p, ss.data());
+    for (int j = 0; j < p; ++j) optim_coef[p + j] = std::sqrt(mdl->cov_pars_tr[0] * ss[j]);
   }
   return 0;
 }

@@ -347,17 +347,10 @@ int gpb_hip_exact_fisher_std_errors(gpb_hip_exact_t* h, int cov_type, double sig
   // sqrt(diag(FI^-1)) through the Cholesky factor (Eigen::LLT in the reference); NaN if it fails
   const double nan = std::numeric_limits<double>::quiet_NaN();
   for (int j = 0; j < 3; ++j) se3_host[j] = nan;
-  double L[3][3] = {{0}};
-  bool ok = true;
-  for (int i = 0; i < 3 && ok; ++i) for (int j = 0; j <= i; ++j) {
-    double v = FI[i][j];
-    for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-    if (i == j) { if (!(v > 0.)) { ok = false; break; } L[i][i] = std::sqrt(v); } else L[i][j] = v / L[j][j];
-  }
-  if (ok) for (int c = 0; c < 3; ++c) {          // (FI^-1)_cc = || L^-1 e_c ||^2
-    double z[3] = {0., 0., 0.}, ss = 0.;
-    for (int i = c; i < 3; ++i) { double v = (i == c) ? 1. : 0.; for (int k = c; k < i; ++k) v -= L[i][k] * z[k]; z[i] = v / L[i][i]; ss += z[i] * z[i]; }
-    if (std::isfinite(ss) && ss >= 0.) se3_host[c] = std::sqrt(ss);
+  if (gpb_sm::cholesky_lower(&FI[0][0], 3, 3)) {
+    double ss[3];
+    gpb_sm::inverse_diagonal(&FI[0][0], 3, 3, ss);
+    for (int c = 0; c < 3; ++c) if (std::isfinite(ss[c]) && ss[c] >= 0.) se3_host[c] = std::sqrt(ss[c]);
   }
   API_END();
 }

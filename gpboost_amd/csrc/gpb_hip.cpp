@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "dense_kernels.h"
+#include "gpb_smallmat.h"
 #include "hist_kernels.h"
 #include "leaf_kernels.h"
 #include "nn_kernels.h"
@@ -2012,24 +2013,11 @@ int gpb_hip_vecchia_newton_leaf_values(gpb_hip_vecchia_t* h, const int32_t* leaf
   std::vector<double> mr(len);
   HIP_OK(hipMemcpyAsync(mr.data(), h->d_leaf_out, sizeof(double) * len, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
-  // L x L Cholesky solve on the host (HTPsiInvH.llt().solve(HTYAux), re_model_template.h:5057)
-  std::vector<double> G((size_t)L * L);
-  for (int i = 0; i < L; ++i) for (int j = 0; j < L; ++j) G[(size_t)i * L + j] = mr[(size_t)i * LP + j];
-  const double* rhs = mr.data() + (size_t)LP * LP;
-  for (int j = 0; j < L; ++j) {
-    double s = G[(size_t)j * L + j];
-    for (int k = 0; k < j; ++k) s -= G[(size_t)j * L + k] * G[(size_t)j * L + k];
-    if (!(s > 0.)) return fail("H^T Psi^-1 H is not positive definite (leaf %d holds no data point?)", j);
-    const double g = std::sqrt(s);
-    G[(size_t)j * L + j] = g;
-    for (int i = j + 1; i < L; ++i) {
-      double t = G[(size_t)i * L + j];
-      for (int k = 0; k < j; ++k) t -= G[(size_t)i * L + k] * G[(size_t)j * L + k];
-      G[(size_t)i * L + j] = t / g;
-    }
-  }
-  for (int i = 0; i < L; ++i) { double t = rhs[i]; for (int k = 0; k < i; ++k) t -= G[(size_t)i * L + k] * leaf_values[k]; leaf_values[i] = t / G[(size_t)i * L + i]; }
-  for (int i = L - 1; i >= 0; --i) { double t = leaf_values[i]; for (int k = i + 1; k < L; ++k) t -= G[(size_t)k * L + i] * leaf_values[k]; leaf_values[i] = t / G[(size_t)i * L + i]; }
+  // L x L Cholesky solve on the host (HTPsiInvH.llt().solve(HTYAux), re_model_template.h:5057), in place in the LP-stride Gram matrix
+  int bad = 0;
+  if (!gpb_sm::cholesky_lower(mr.data(), L, LP, nullptr, &bad)) return fail("H^T Psi^-1 H is not positive definite (leaf %d holds no data point?)", bad);
+  std::copy(mr.data() + (size_t)LP * LP, mr.data() + (size_t)LP * LP + L, leaf_values);
+  gpb_sm::cholesky_solve(mr.data(), L, LP, leaf_values);
   API_END();
 }
 

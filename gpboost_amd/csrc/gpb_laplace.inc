@@ -839,50 +839,18 @@ enum : int { LAP_RESET_MODE = 1, LAP_KEEP_GRAD_STATE = 2 };
 // "fitc": C = cross-covariance with the inducing points, Sigma_m (jittered diagonal, JITTER_MULT_IP_FITC_FSA = 1 + 1e-6), V = C L_m^-T and ||V_i||^2 at this evaluation's
 // parameters (Calc_FITC_Preconditioner_Vecchia, re_model_template.h:9577-9591): the n x k parts with the cross-covariance / product kernels of the full-scale
 // approximation (vif_kernels.hip), the k x k part on the host.
-double pc_host_cov(int cov, double d, double var, double a) {
-  const double r = a * d;
-  if (cov == 0) return var * std::exp(-r);
-  if (cov == 1) return var * (1.0 + r) * std::exp(-r);
-  return var * (1.0 + r + r * r / 3.0) * std::exp(-r);
-}
-double pc_host_cov_grad(int cov, double d, double var, double a) {      // d / d log a of var k(a d): GradientRangeMaternShape0_5 / 1_5 / 2_5 on the transformed scale (cov_fcts.h:2535-2554)
-  const double r = a * d;
-  if (cov == 0) return -var * r * std::exp(-r);
-  if (cov == 1) return -var * r * r * std::exp(-r);
-  return -var * r * r * (1.0 + r) / 3.0 * std::exp(-r);
-}
-// Sigma_m of k inducing points (k x 3 row-major) with the jittered diagonal (JITTER_MULT_IP_FITC_FSA = 1 + 1e-6), the inverse of its lower Cholesky factor L_m (row-major) and
-// log|Sigma_m| -- the k x k host part of "fitc" and of the full-scale approximation.  -1: not positive definite
-int ip_cov_factor(const std::vector<double>& ip3, int k, int cov_type, double var, double a, std::vector<double>* Sm_out, std::vector<double>* Li_out, double* logdet) {
-  std::vector<double>& Sm = *Sm_out; std::vector<double>& Li = *Li_out;
-  Sm.assign((size_t)k * k, 0.0); Li.assign((size_t)k * k, 0.0);
-  std::vector<double> Lm((size_t)k * k, 0.0);
-  for (int p = 0; p < k; ++p)
-    for (int q = 0; q <= p; ++q) {
-      double d2 = 0.0; for (int c = 0; c < 3; ++c) { const double t = ip3[(size_t)p * 3 + c] - ip3[(size_t)q * 3 + c]; d2 += t * t; }
-      Sm[(size_t)p * k + q] = Sm[(size_t)q * k + p] = pc_host_cov(cov_type, std::sqrt(d2), var, a);
-    }
-  for (int p = 0; p < k; ++p) Sm[(size_t)p * k + p] *= 1.0 + 1e-6;
+namespace sm = gpb_sm;
+// Sigma_m of k inducing points (k x 3 row-major) with the jittered diagonal, the inverse of its lower Cholesky factor L_m (row-major) and log|Sigma_m| -- the k x k host
+// part of "fitc" and of the full-scale approximation.  -1: not positive definite
+int ip_cov_factor(const std::vector<double>& ip3, int k, int cov_type, double var, double a, std::vector<double>* Sm, std::vector<double>* Li, double* logdet) {
+  Sm->resize((size_t)k * k); Li->resize((size_t)k * k);
+  sm::ip_cov(ip3.data(), k, 3, sm::IpLayout::RowMajorKx3, sm::MaternForm::LaplacePaths, cov_type, var, a, Sm->data(), nullptr);
+  for (int p = 0; p < k; ++p) (*Sm)[(size_t)p * k + p] *= sm::JITTER_MULT_IP_FITC_FSA;
+  std::vector<double> Lm(*Sm);
   double ld = 0.0;
-  for (int j = 0; j < k; ++j) {
-    double sd = Sm[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sd -= Lm[(size_t)j * k + p] * Lm[(size_t)j * k + p];
-    if (!(sd > 0.0)) return -1;
-    const double l = std::sqrt(sd);
-    Lm[(size_t)j * k + j] = l; ld += std::log(l);
-    for (int i = j + 1; i < k; ++i) {
-      double tv = Sm[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= Lm[(size_t)i * k + p] * Lm[(size_t)j * k + p];
-      Lm[(size_t)i * k + j] = tv / l;
-    }
-  }
+  if (!sm::cholesky_lower(Lm.data(), k, k, &ld)) return -1;
   *logdet = 2.0 * ld;
-  for (int c = 0; c < k; ++c)                                 // column c of L_m^-1 by forward substitution
-    for (int i = c; i < k; ++i) {
-      double tv = (i == c) ? 1.0 : 0.0;
-      for (int p = c; p < i; ++p) tv -= Lm[(size_t)i * k + p] * Li[(size_t)p * k + c];
-      Li[(size_t)i * k + c] = tv / Lm[(size_t)i * k + i];
-    }
+  sm::tri_inverse_lower(Lm.data(), k, k, Li->data());
   return 0;
 }
 int pc_factor_fitc(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double var, double a, hipStream_t st) {
@@ -1036,33 +1004,9 @@ int pc_refresh(LaplaceState* s, int n, const double* W, hipStream_t st, int* bad
   HIP_OK(hipStreamSynchronize(st));
   for (int p = 0; p < k; ++p) for (int q = 0; q <= p; ++q) C[(size_t)p * k + q] = G[(size_t)p * (p + 1) / 2 + q] + (fitc ? s->pc_Sm[(size_t)p * k + q] : (p == q ? 1.0 : 0.0));
   double ld = 0.0;
-  for (int j = 0; j < k; ++j) {                       // lower Cholesky factor in place
-    double sdiag = C[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sdiag -= C[(size_t)j * k + p] * C[(size_t)j * k + p];
-    if (!(sdiag > 0.0) || !std::isfinite(sdiag)) { *bad = 1; return 0; }
-    const double l = std::sqrt(sdiag);
-    C[(size_t)j * k + j] = l; ld += std::log(l);
-    for (int i = j + 1; i < k; ++i) {
-      double tv = C[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= C[(size_t)i * k + p] * C[(size_t)j * k + p];
-      C[(size_t)i * k + j] = tv / l;
-    }
-  }
+  if (!sm::cholesky_lower(C.data(), k, k, &ld)) { *bad = 1; return 0; }
   s->pc_logdet = fitc ? 2.0 * ld - s->pc_logdet_Sm - sum_log_wp : 2.0 * ld;      // fitc: log|P| itself; pivoted_cholesky: log|I_k + L_k' W L_k| (log|P| = that - log|W|)
-  std::vector<double> x(k);
-  for (int c = 0; c < k; ++c) {                       // column c of the inverse
-    for (int i = 0; i < k; ++i) {
-      double tv = (i == c) ? 1.0 : 0.0;
-      for (int p = 0; p < i; ++p) tv -= C[(size_t)i * k + p] * x[p];
-      x[i] = tv / C[(size_t)i * k + i];
-    }
-    for (int i = k - 1; i >= 0; --i) {
-      double tv = x[i];
-      for (int p = i + 1; p < k; ++p) tv -= C[(size_t)p * k + i] * x[p];
-      x[i] = tv / C[(size_t)i * k + i];
-    }
-    for (int i = 0; i < k; ++i) M[(size_t)i * k + c] = x[i];
-  }
+  sm::spd_inverse_by_solves(C.data(), k, k, M.data());
   HIP_OK(hipMemcpyAsync(s->d_pcM, M.data(), sizeof(double) * (size_t)k * k, hipMemcpyHostToDevice, st));
   HIP_OK(hipStreamSynchronize(st));
   if (fitc) s->pc_Minv = M;
@@ -1110,47 +1054,20 @@ int vif_lap_factor(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double v
   for (int p = 0; p < k; ++p) for (int q = 0; q <= p; ++q) Cm[(size_t)p * k + q] = Sm[(size_t)p * k + q] + G[(size_t)p * kq + q];
   s->vif_M.assign((size_t)k * k, 0.0);
   for (int p = 0; p < k; ++p) for (int q = 0; q <= p; ++q) s->vif_M[(size_t)p * k + q] = s->vif_M[(size_t)q * k + p] = Cm[(size_t)p * k + q];
-  for (int j = 0; j < k; ++j) {
-    double sd = Cm[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sd -= Cm[(size_t)j * k + p] * Cm[(size_t)j * k + p];
-    if (!(sd > 0.0) || !std::isfinite(sd)) return fail("the Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
-    const double l = std::sqrt(sd);
-    Cm[(size_t)j * k + j] = l;
-    for (int i = j + 1; i < k; ++i) {
-      double tv = Cm[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= Cm[(size_t)i * k + p] * Cm[(size_t)j * k + p];
-      Cm[(size_t)i * k + j] = tv / l;
-    }
-  }
-  s->vif_logdet_M = 0.0;
-  for (int j = 0; j < k; ++j) s->vif_logdet_M += 2.0 * std::log(Cm[(size_t)j * k + j]);
+  double ld = 0.0;
+  if (!sm::cholesky_lower(Cm.data(), k, k, &ld)) return fail("the Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
+  s->vif_logdet_M = 2.0 * ld;
   h->has_factor = true;
   return 0;
 }
-// inverse of a symmetric positive definite k x k matrix by its Cholesky factor (in place in A); *logdet its log-determinant; -1: not positive definite
-int spd_inverse_kk(std::vector<double>& A, int k, double* logdet) {
+// A <- A^-1 for a symmetric positive definite k x k matrix, by solves with its Cholesky factor; *logdet its log-determinant; false: not positive definite
+bool spd_invert(std::vector<double>& A, int k, double* logdet) {
   std::vector<double> C(A);
   double ld = 0.0;
-  for (int j = 0; j < k; ++j) {
-    double sd = C[(size_t)j * k + j];
-    for (int p = 0; p < j; ++p) sd -= C[(size_t)j * k + p] * C[(size_t)j * k + p];
-    if (!(sd > 0.0) || !std::isfinite(sd)) return -1;
-    const double l = std::sqrt(sd);
-    C[(size_t)j * k + j] = l; ld += 2.0 * std::log(l);
-    for (int i = j + 1; i < k; ++i) {
-      double tv = C[(size_t)i * k + j];
-      for (int p = 0; p < j; ++p) tv -= C[(size_t)i * k + p] * C[(size_t)j * k + p];
-      C[(size_t)i * k + j] = tv / l;
-    }
-  }
-  std::vector<double> x(k);
-  for (int c = 0; c < k; ++c) {
-    for (int i = 0; i < k; ++i) { double tv = (i == c) ? 1.0 : 0.0; for (int p = 0; p < i; ++p) tv -= C[(size_t)i * k + p] * x[p]; x[i] = tv / C[(size_t)i * k + i]; }
-    for (int i = k - 1; i >= 0; --i) { double tv = x[i]; for (int p = i + 1; p < k; ++p) tv -= C[(size_t)p * k + i] * x[p]; x[i] = tv / C[(size_t)i * k + i]; }
-    for (int i = 0; i < k; ++i) A[(size_t)i * k + c] = x[i];
-  }
-  *logdet = ld;
-  return 0;
+  if (!sm::cholesky_lower(C.data(), k, k, &ld)) return false;
+  sm::spd_inverse_by_solves(C.data(), k, k, A.data());
+  *logdet = 2.0 * ld;
+  return true;
 }
 // the storage-order copies of V and B C, 1 / D, the small multipliers (after build_levels: needs sigma)
 int vif_lap_pack(gpb_hip_vecchia_t* h, LaplaceState* s, bool with_grad, hipStream_t st) {
@@ -1215,16 +1132,10 @@ int vif_qf_enqueue(LaplaceState* s, int n, const double* Bx, int slot, hipStream
 }
 double vif_qf_value(const LaplaceState* s, int slot) {
   const int k = s->vif_kk;
-  const double* y = s->h_vk + (size_t)slot * k;
-  const std::vector<double>& C = s->vif_cholM;
-  std::vector<double> x(k);
+  std::vector<double> x(s->h_vk + (size_t)slot * k, s->h_vk + (size_t)(slot + 1) * k);
+  sm::solve_lower(s->vif_cholM.data(), k, k, x.data());
   double r = 0.0;
-  for (int i = 0; i < k; ++i) {              // |L^-1 y|^2
-    double tv = y[i];
-    for (int p = 0; p < i; ++p) tv -= C[(size_t)i * k + p] * x[p];
-    x[i] = tv / C[(size_t)i * k + i];
-    r += x[i] * x[i];
-  }
+  for (int i = 0; i < k; ++i) r += x[i] * x[i];      // |L^-1 y|^2
   return r;
 }
 
@@ -1366,7 +1277,7 @@ struct LapSolver {
     HIP_OK(hipMemcpyAsync(G.data(), s->d_vifx2, sizeof(double) * npairs, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     for (int p = 0; p < vk; ++p) for (int q = 0; q <= p; ++q) MM[(size_t)p * vk + q] = MM[(size_t)q * vk + p] = s->vif_M[(size_t)p * vk + q] - G[(size_t)p * (p + 1) / 2 + q];
-    if (spd_inverse_kk(MM, vk, &s->vif_logdet_MM)) { *pbad = 1; return 0; }
+    if (!spd_invert(MM, vk, &s->vif_logdet_MM)) { *pbad = 1; return 0; }
     HIP_OK(hipMemcpy(s->d_vifMinv + (size_t)vk * vk, MM.data(), sizeof(double) * (size_t)vk * vk, hipMemcpyHostToDevice));
     return 0;
   }
@@ -1641,7 +1552,7 @@ int lap_eval_operators(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs&
     if (!s->d_vifMinv) HIP_OK(hipMalloc(&s->d_vifMinv, sizeof(double) * (size_t)2 * vk * vk));
     std::vector<double> Mi(s->vif_M);
     double ldm = 0.0;
-    if (spd_inverse_kk(Mi, vk, &ldm)) return fail("the Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
+    if (!spd_invert(Mi, vk, &ldm)) return fail("the Woodbury matrix of the full-scale Vecchia approximation is not positive definite");
     HIP_OK(hipMemcpy(s->d_vifMinv, Mi.data(), sizeof(double) * (size_t)vk * vk, hipMemcpyHostToDevice));
   }
   return 0;
@@ -1922,23 +1833,11 @@ struct VifGradHost {
   double *d_dgrad[2] = { nullptr, nullptr };
 };
 namespace {
-void sym_from_packed(const std::vector<double>& G, int k, std::vector<double>* out) {
-  out->assign((size_t)k * k, 0.0);
-  for (int p = 0; p < k; ++p) for (int q = 0; q <= p; ++q) (*out)[(size_t)p * k + q] = (*out)[(size_t)q * k + p] = G[(size_t)p * (p + 1) / 2 + q];
-}
-void matmul_kk(const std::vector<double>& A, const std::vector<double>& B, int k, std::vector<double>* C) {
-  C->assign((size_t)k * k, 0.0);
-  for (int i = 0; i < k; ++i) for (int p = 0; p < k; ++p) { const double a = A[(size_t)i * k + p]; if (a != 0.0) for (int j = 0; j < k; ++j) (*C)[(size_t)i * k + j] += a * B[(size_t)p * k + j]; }
-}
 // x <- (L L')^-1 x given Linv = L^-1 (lower, row-major)
 void apply_linv_sym(const std::vector<double>& Linv, int k, const double* x, double* out) {
   std::vector<double> t(k);
   for (int i = 0; i < k; ++i) { double a = 0.0; for (int p = 0; p <= i; ++p) a += Linv[(size_t)i * k + p] * x[p]; t[i] = a; }
   for (int i = 0; i < k; ++i) { double a = 0.0; for (int p = i; p < k; ++p) a += Linv[(size_t)p * k + i] * t[p]; out[i] = a; }
-}
-void chol_solve_kk(const std::vector<double>& C, int k, const double* b, double* x) {      // (C C')^-1 b, C lower
-  for (int i = 0; i < k; ++i) { double tv = b[i]; for (int p = 0; p < i; ++p) tv -= C[(size_t)i * k + p] * x[p]; x[i] = tv / C[(size_t)i * k + i]; }
-  for (int i = k - 1; i >= 0; --i) { double tv = x[i]; for (int p = i + 1; p < k; ++p) tv -= C[(size_t)p * k + i] * x[p]; x[i] = tv / C[(size_t)i * k + i]; }
 }
 }  // namespace
 int vif_grad_prepare(gpb_hip_vecchia_t* h, LaplaceState* s, VifGradHost* vg, hipStream_t st) {
@@ -1946,30 +1845,19 @@ int vif_grad_prepare(gpb_hip_vecchia_t* h, LaplaceState* s, VifGradHost* vg, hip
   const int K = std::max(k, kp);
   vg->k = k; vg->kp = kp;
   const int cov = s->g_cov; const double var = s->g_var, a = s->g_a;
-  auto ip_mats = [&](const std::vector<double>& ip3, int kk, std::vector<double>* d0, std::vector<double>* d1) {
-    d0->assign((size_t)kk * kk, 0.0); d1->assign((size_t)kk * kk, 0.0);
-    for (int p = 0; p < kk; ++p)
-      for (int q = 0; q <= p; ++q) {
-        double d2 = 0.0; for (int c = 0; c < 3; ++c) { const double tv = ip3[(size_t)p * 3 + c] - ip3[(size_t)q * 3 + c]; d2 += tv * tv; }
-        const double dd = std::sqrt(d2);
-        (*d0)[(size_t)p * kk + q] = (*d0)[(size_t)q * kk + p] = pc_host_cov(cov, dd, var, a);
-        (*d1)[(size_t)p * kk + q] = (*d1)[(size_t)q * kk + p] = pc_host_cov_grad(cov, dd, var, a);
-      }
-  };
-  ip_mats(h->vif_ip_host, k, &vg->dSm[0], &vg->dSm[1]);
-  ip_mats(s->pc_ip, kp, &vg->dSmp[0], &vg->dSmp[1]);
+  const size_t k2 = (size_t)k * k, kp2 = (size_t)kp * kp;
+  for (int p = 0; p < 2; ++p) { vg->dSm[p].resize(k2); vg->dSmp[p].resize(kp2); }
+  sm::ip_cov(h->vif_ip_host.data(), k, 3, sm::IpLayout::RowMajorKx3, sm::MaternForm::LaplacePaths, cov, var, a, vg->dSm[0].data(), vg->dSm[1].data());
+  sm::ip_cov(s->pc_ip.data(), kp, 3, sm::IpLayout::RowMajorKx3, sm::MaternForm::LaplacePaths, cov, var, a, vg->dSmp[0].data(), vg->dSmp[1].data());
   // ---- dA / dD of the latent residual process (Vecchia_utils.cpp:1503-1524, :1640-1656): the VIF derivative kernel; of its inputs only Si = Sigma_m^-1, N0 = 2 Si - Si dSm0 Si
   //      and negMp1 = -Si dSm1 Si matter here (the Gaussian path's sums are not used) ----
-  std::vector<double> Si((size_t)k * k), N0, negMp1, Iw((size_t)k * k, 0.0), w0(k, 0.0), tmp, tmp2;
-  for (int i = 0; i < k; ++i) for (int j = 0; j <= i; ++j) {
-    double acc = 0.0; for (int p = i; p < k; ++p) acc += s->vif_Linv[(size_t)p * k + i] * s->vif_Linv[(size_t)p * k + j];
-    Si[(size_t)i * k + j] = Si[(size_t)j * k + i] = acc;
-  }
+  std::vector<double> Si(k2), N0(k2), negMp1(k2), Iw(k2, 0.0), w0(k, 0.0), tmp((size_t)K * K), tmp2(k2);
+  sm::spd_inverse_from_tri(s->vif_Linv.data(), k, Si.data());
   for (int i = 0; i < k; ++i) Iw[(size_t)i * k + i] = 1.0;
-  matmul_kk(Si, vg->dSm[0], k, &tmp); matmul_kk(tmp, Si, k, &tmp2);
-  N0.resize((size_t)k * k); for (size_t e = 0; e < N0.size(); ++e) N0[e] = 2.0 * Si[e] - tmp2[e];
-  matmul_kk(Si, vg->dSm[1], k, &tmp); matmul_kk(tmp, Si, k, &tmp2);
-  negMp1.resize((size_t)k * k); for (size_t e = 0; e < negMp1.size(); ++e) negMp1[e] = -tmp2[e];
+  sm::matmul(Si.data(), vg->dSm[0].data(), k, tmp.data()); sm::matmul(tmp.data(), Si.data(), k, tmp2.data());
+  for (size_t e = 0; e < k2; ++e) N0[e] = 2.0 * Si[e] - tmp2[e];
+  sm::matmul(Si.data(), vg->dSm[1].data(), k, tmp.data()); sm::matmul(tmp.data(), Si.data(), k, tmp2.data());
+  for (size_t e = 0; e < k2; ++e) negMp1[e] = -tmp2[e];
   double sums12[GPB_VIF_GRAD_TERMS];
   if (vif_grad_sums_impl(h, cov, var, a, Iw.data(), Si.data(), N0.data(), negMp1.data(), w0.data(), 1, sums12, true)) return -1;
   HIP_OK(hipMemcpyAsync(s->d_dA, h->d_vdA + (size_t)n * m, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToDevice, st));
@@ -1994,7 +1882,8 @@ int vif_grad_prepare(gpb_hip_vecchia_t* h, LaplaceState* s, VifGradHost* vg, hip
     HIP_OK(gpb::pc_gram(L, Wv, n, kk, s->d_pcpart, s->d_vifq, st));
     HIP_OK(hipMemcpyAsync(G.data(), s->d_vifq, sizeof(double) * npairs, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    sym_from_packed(G, kk, out);
+    out->resize((size_t)kk * kk);
+    sm::sym_from_packed(G.data(), kk, out->data());
     return 0;
   };
   const size_t nk = (size_t)n * k;
@@ -2021,15 +1910,12 @@ int vif_grad_prepare(gpb_hip_vecchia_t* h, LaplaceState* s, VifGradHost* vg, hip
   }
   // ---- the preconditioner: derivative of its diagonal (:5478-5486), sigma_woodbury_grad_preconditioner (:5490-5498) ----
   {
-    std::vector<double> Sip((size_t)kp * kp), M2;
-    for (int i = 0; i < kp; ++i) for (int j = 0; j <= i; ++j) {
-      double acc = 0.0; for (int p = i; p < kp; ++p) acc += s->pc_Linv[(size_t)p * kp + i] * s->pc_Linv[(size_t)p * kp + j];
-      Sip[(size_t)i * kp + j] = Sip[(size_t)j * kp + i] = acc;
-    }
+    std::vector<double> Sip(kp2), M2(kp2);
+    sm::spd_inverse_from_tri(s->pc_Linv.data(), kp, Sip.data());
     std::vector<double> Gp, ga, gb, gc;
     if (gram(s->d_pcL, s->d_pcwp, kp, &Gp)) return -1;
     for (int p = 0; p < 2; ++p) {
-      matmul_kk(Sip, vg->dSmp[p], kp, &tmp); matmul_kk(tmp, Sip, kp, &M2);
+      sm::matmul(Sip.data(), vg->dSmp[p].data(), kp, tmp.data()); sm::matmul(tmp.data(), Sip.data(), kp, M2.data());
       HIP_OK(hipMemcpyAsync(s->d_vifq, Sip.data(), sizeof(double) * Sip.size(), hipMemcpyHostToDevice, st));
       HIP_OK(hipMemcpyAsync(s->d_vifq + (size_t)kp * kp, M2.data(), sizeof(double) * M2.size(), hipMemcpyHostToDevice, st));
       HIP_OK(gpb::pc_row_quad(s->d_pcL, p == 0 ? s->d_pcL : s->d_pcdL, s->d_vifq, s->d_vifq + (size_t)kp * kp, n, kp, vg->dSmp[p][0], vg->d_dgrad[p], st));
@@ -2097,12 +1983,12 @@ double vif_grad_assemble(const LaplaceState* s, const VifGradHost& vg, int j, in
   // ---- x' SigmaI_deriv_mode for x = mode, sv ----
   const double* yC = vg.yC.data(); const double* ydC = (j == 0) ? vg.yC.data() : vg.ydC.data();
   const int a1col = (j == 0) ? 0 : 2;
-  std::vector<double> y2(k), wsol(k), tmp(k), kv(k), Mgw(k);
-  for (int q = 0; q < k; ++q) y2[q] = -yC[q];                                   // C' S mode
-  chol_solve_kk(s->vif_cholM, k, y2.data(), wsol.data());
+  std::vector<double> wsol(k), kv(k), Mgw(k);
+  for (int q = 0; q < k; ++q) wsol[q] = -yC[q];                                 // C' S mode
+  sm::cholesky_solve(s->vif_cholM.data(), k, k, wsol.data());
   matvec(vg.Mg[j], wsol.data(), k, Mgw.data());
-  for (int q = 0; q < k; ++q) tmp[q] = yC[(size_t)a1col * k + q] + (-ydC[q]) - Mgw[q];       // C' a1 + dC' S mode - Mg wsol
-  chol_solve_kk(s->vif_cholM, k, tmp.data(), kv.data());
+  for (int q = 0; q < k; ++q) kv[q] = yC[(size_t)a1col * k + q] + (-ydC[q]) - Mgw[q];        // C' a1 + dC' S mode - Mg wsol
+  sm::cholesky_solve(s->vif_cholM.data(), k, k, kv.data());
   double val[2];
   for (int x = 0; x < 2; ++x) {
     const double xa1 = x == 0 ? mSm0 : sSm0;
@@ -2483,7 +2369,8 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   HIP_OK(gpb::lap_B(lv, n, mode, Bm, 1, 1, st));
   if (vif_qf_enqueue(s, n, Bm, 0, st)) return -1;
   HIP_OK(hipStreamSynchronize(st));
-  chol_solve_kk(s->vif_cholM, k, s->h_vk, w0.data());
+  std::copy(s->h_vk, s->h_vk + k, w0.begin());
+  sm::cholesky_solve(s->vif_cholM.data(), k, k, w0.data());
   if (vif_small(s, n, k, 1, 1)) return -1;
   HIP_OK(hipMemcpyAsync(s->d_vifx2, w0.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
   HIP_OK(gpb::pc_combine(s->d_vifC, s->d_vifones, mode, s->d_vifx2, n, k, 1, 1, 1, dir, st));          // s (storage order)
@@ -2615,7 +2502,7 @@ int vif_laplace_predict_impl(gpb_hip_vecchia_t* h, int32_t n_pred, const double*
   std::vector<double> M2((size_t)k * k);
   for (int p = 0; p < k; ++p) for (int q = 0; q < k; ++q) M2[(size_t)p * k + q] = s->vif_Sm[(size_t)p * k + q] + 0.5 * (G2[(size_t)p * k + q] + G2[(size_t)q * k + p]);
   double ld2 = 0.0;
-  if (spd_inverse_kk(M2, k, &ld2)) return fail("Laplace prediction Woodbury matrix: not positive definite");      // CheckCholeskyFactorization, likelihoods.h:8463
+  if (!spd_invert(M2, k, &ld2)) return fail("Laplace prediction Woodbury matrix: not positive definite");      // CheckCholeskyFactorization, likelihoods.h:8463
   std::vector<double> ap(k), vp(k), m1(k), m2(k), m4(k);
   // (covariance matrix, :8489-8504: the same terms between two prediction points -- the per-point k-vectors are kept)
   std::vector<double> APm, VPm, M1m, M2m, M4m;

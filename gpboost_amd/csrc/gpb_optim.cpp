@@ -3,6 +3,7 @@
 // (State) with its gradient descent; the Laplace problem (LapState) with its gradient descent; the coefficient / auxiliary-parameter problem (LapCoefState)
 // with its gradient descent; the entry points.  Every solver exists once; a model family supplies a small "problem" adapter or an objective lambda.
 #include "gpb_optim.h"
+#include "gpb_smallmat.h"
 
 #include <algorithm>
 #include <cmath>
@@ -266,24 +267,10 @@ int nelder_mead(F&& f, int n, double* x, const GpbOptimConfig& cfg, double delta
 // inv_diag[c], c indexing sel.  false: not positive definite (inv_diag untouched).
 bool spd_inverse_diagonal(const std::vector<double>& H, int N, const std::vector<int>& sel, std::vector<double>& inv_diag) {
   const int E = (int)sel.size();
-  std::vector<double> L((size_t)E * E, 0.), col(E);
-  for (int i = 0; i < E; ++i)
-    for (int j = 0; j <= i; ++j) {
-      double acc = H[(size_t)sel[i] * N + sel[j]];
-      for (int k = 0; k < j; ++k) acc -= L[(size_t)i * E + k] * L[(size_t)j * E + k];
-      if (i == j) { if (!(acc > 0.) || !std::isfinite(acc)) return false; L[(size_t)i * E + i] = std::sqrt(acc); }
-      else L[(size_t)i * E + j] = acc / L[(size_t)j * E + j];
-    }
-  for (int c = 0; c < E; ++c) {
-    double ss = 0.;
-    for (int i = c; i < E; ++i) {
-      double acc = i == c ? 1. : 0.;
-      for (int k = c; k < i; ++k) acc -= L[(size_t)i * E + k] * col[k];
-      col[i] = acc / L[(size_t)i * E + i];
-      ss += col[i] * col[i];
-    }
-    inv_diag[c] = ss;
-  }
+  std::vector<double> L((size_t)E * E, 0.);
+  for (int i = 0; i < E; ++i) for (int j = 0; j <= i; ++j) L[(size_t)i * E + j] = H[(size_t)sel[i] * N + sel[j]];
+  if (!gpb_sm::cholesky_lower(L.data(), E, E)) return false;
+  gpb_sm::inverse_diagonal(L.data(), E, E, inv_diag.data());
   return true;
 }
 

@@ -5,7 +5,7 @@
      PredCall        the arguments of the C entry point as passed, and what pred_resolve made of them
      pred_path       which of the five model paths a call takes
      predict_*       one function per path: its refusals in its own order, pred_resolve, the device calls, the host algebra
-     shared pieces   bp_inverse_rows (forward substitution with Bp = I - A_pp), lower_solve_rows, write_second_moments, scatter_prediction,
+     shared pieces   bp_inverse_rows (forward substitution with Bp = I - A_pp), write_second_moments, scatter_prediction,
                      pred_neighbor_count, location_parameter, add_linear_predictor
    Everything here is host orchestration.  Its sums are taken in a fixed order (neighbour slots ascending, inner index ascending), and
    tests/test_zz_predict_paths_gpu.py holds every result and every message to a recording, bit for bit: an edit that reorders a sum or two checks shows there. */
@@ -197,18 +197,6 @@ int bp_inverse_rows(int n_obs, int n_pred, int m_used, const int32_t* nn, const 
   return 0;
 }
 
-// rows (n x k, in place) <- rows Lw^-T, i.e. row_i <- L_W^-1 row_i by forward substitution; Lw: k x k lower triangular, row-major
-void lower_solve_rows(const std::vector<double>& Lw, int k, int n, double* rows) {
-  for (int i = 0; i < n; ++i) {
-    double* t = rows + (size_t)i * k;
-    for (int r = 0; r < k; ++r) {
-      double v = t[r];
-      for (int j = 0; j < r; ++j) v -= Lw[(size_t)r * k + j] * t[j];
-      t[r] = v / Lw[(size_t)r * k + r];
-    }
-  }
-}
-
 /* Second moments of np points: v_ij = sigma2 f(i, j), plus diag_shift on the diagonal -- over the lower triangle with a symmetric store into cov_out
    (np x np) if that is asked for, over the diagonal otherwise; var_out (np) gets the diagonal.  Either output may be null.  Where a path removes or adds the
    error variance INSIDE the scaled sum, its f does that and diag_shift is 0. */
@@ -294,7 +282,7 @@ int predict_vif_gauss(REModelHip* mdl, PredCall& c) {
   if (second) {
     // T_i = L_W^-1 (B C)_i: var_p = D_p + ||T_p||^2 and -- obs-only: the residuals of two prediction points are independent given the observed ones
     // (Bp = I) -- cov_pq = T_p . T_q off the diagonal
-    lower_solve_rows(vs.Lw, kv, np, BC.data());
+    gpb_sm::solve_lower_rows(vs.Lw.data(), kv, kv, np, BC.data());      // rows <- rows L_W^-T
     const double* T = BC.data();
     const double sigma2 = c.tr[0], latent = c.response ? 0. : 1.;
     const auto tt = [&](int i, int j) { double qq = 0.; for (int r = 0; r < kv; ++r) qq += T[(size_t)i * kv + r] * T[(size_t)j * kv + r]; return qq; };
@@ -448,7 +436,7 @@ int predict_exact(REModelHip* mdl, PredCall& c) {
   const double nug = c.response ? 1. : 0.;
   if (second)
     write_second_moments(c.var ? c.out + np : nullptr, c.cov ? c.out + np : nullptr, np, c.tr[0], 0., [&](int i, int j) {
-      const double prior = i == j ? c.tr[1] + nug : matern_host(mdl->cov_type, c.tr[1], c.tr[2] * std::sqrt(sq_dist(c.cp, np, mdl->d, i, j)));
+      const double prior = i == j ? c.tr[1] + nug : gpb_sm::matern_gaussian_paths(mdl->cov_type, c.tr[1], c.tr[2] * std::sqrt(sq_dist(c.cp, np, mdl->d, i, j)));
       return prior - q[(size_t)i * np + j];
     });
   mdl->yaux_valid = false;
@@ -616,7 +604,7 @@ int predict_clusters(REModelHip* mdl, PredCall& c) {
       if (c.cov) {
         if (npc > mdl->num_neighbors + 1) return set_error("GPB_PredictREModel: covariance matrix of %d prediction points in a cluster without observations (more than num_neighbors + 1 = %d) %s", npc, mdl->num_neighbors + 1, scope);
         for (int a1 = 0; a1 < npc; ++a1) for (int b1 = 0; b1 < npc; ++b1)
-          outc[npc + (size_t)a1 * npc + b1] = a1 == b1 ? vdiag : c.tr[0] * c.tr[1] * matern_host(mdl->cov_type, 1., c.tr[2] * std::sqrt(sq_dist(cc.data(), npc, d, a1, b1)));
+          outc[npc + (size_t)a1 * npc + b1] = a1 == b1 ? vdiag : c.tr[0] * c.tr[1] * gpb_sm::matern_gaussian_paths(mdl->cov_type, 1., c.tr[2] * std::sqrt(sq_dist(cc.data(), npc, d, a1, b1)));
       }
     } else {
       // a view of cluster ci as a one-cluster model: shares the device state and the resident response, owns nothing
