@@ -830,6 +830,82 @@ int gpb_hip_vecchia_laplace_ops_check(gpb_hip_vecchia_t* h, int32_t op, int32_t 
   API_END();
 }
 
+// Test entry (include/gpb_hip.h): the likelihood launchers of laplace_kernels.h on the caller's arrays, no handle and no formula of its own.  op 0: lap_newton_setup,
+// lap_objective (all rows, then one launch per row with n = 1 and advanced pointers for the first n_each rows), lap_third_deriv, lap_grad_F / lap_grad_F_map and, for a
+// likelihood with auxiliary parameters, lap_aux_grad -- the last two with the dW3 the third-derivative launch just wrote, as in production.  op 1: lap_math_probe.
+int gpb_hip_laplace_lik_check(int32_t op, int32_t lik, int32_t n, int32_t n_data, const int32_t* re_ptr, const int32_t* y_int, const double* y_real, const double* weights,
+                              const double* fixed_effects, const double* mode, const double* D, const double* Bx, const double* dld, const double* sv, double aux, double aux2,
+                              int32_t n_each, double* W, double* rhs, double* dw, double* rdw, double* out2, double* ll_each, double* dW3, double* gradF, double* out3) {
+  API_BEGIN();
+  if (op != 0 && op != 1) return fail("gpb_hip_laplace_lik_check: op = %d (0: the likelihood launchers, 1: the math probe)", op);
+  if (n < 1 || n > (1 << 24) || !mode || !W) return fail("gpb_hip_laplace_lik_check: n = %d (1 .. 2^24), mode and W are needed", n);
+  if (check_device()) return -1;
+  const auto up = [](auto& buf, const auto* src, size_t cnt) -> hipError_t {
+    hipError_t e = buf.alloc(cnt);
+    return e != hipSuccess ? e : hipMemcpy(buf, src, sizeof(*src) * cnt, hipMemcpyHostToDevice);
+  };
+  const auto nan_filled = [](DevBuf<double>& buf, size_t cnt) -> hipError_t {
+    const std::vector<double> v(cnt, std::nan(""));
+    hipError_t e = buf.alloc(cnt);
+    return e != hipSuccess ? e : hipMemcpy(buf, v.data(), sizeof(double) * cnt, hipMemcpyHostToDevice);
+  };
+  const auto down = [](double* dst, const DevBuf<double>& buf, size_t cnt) -> hipError_t { return hipMemcpy(dst, buf, sizeof(double) * cnt, hipMemcpyDeviceToHost); };
+  DevBuf<double> d_mode, d_W;
+  HIP_OK(up(d_mode, mode, n));
+  HIP_OK(nan_filled(d_W, n));
+  if (op == 1) {
+    HIP_OK(gpb::lap_math_probe(lik, d_mode, n, d_W, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(down(W, d_W, n));
+    return 0;
+  }
+  if (!gpb::lik_valid(lik)) return fail("gpb_hip_laplace_lik_check: likelihood id %d", lik);
+  if (!D || !dld || !sv || !rhs || !dw || !rdw || !out2 || !ll_each || !dW3 || !gradF || !out3) return fail("gpb_hip_laplace_lik_check: null argument");
+  if ((y_int != nullptr) == (y_real != nullptr)) return fail("gpb_hip_laplace_lik_check: exactly one of the int and the real response");
+  if (y_real ? !gpb::lik_accepts_real(lik) : gpb::lik_real_only(lik)) return fail("gpb_hip_laplace_lik_check: %s does not take this kind of response", gpb::lik_name(lik));
+  if (n_each < 0 || n_each > n) return fail("gpb_hip_laplace_lik_check: n_each = %d (0 .. n)", n_each);
+  if (re_ptr) {
+    bool ok = re_ptr[0] == 0 && re_ptr[n] == n_data;
+    for (int i = 0; ok && i < n; ++i) ok = re_ptr[i] <= re_ptr[i + 1];
+    if (!ok) return fail("gpb_hip_laplace_lik_check: re_ptr must rise from 0 to n_data");
+  } else if (n_data != n) return fail("gpb_hip_laplace_lik_check: n_data = %d without re_ptr (n = %d)", n_data, n);
+  if (n_data < 1 || n_data > (1 << 24)) return fail("gpb_hip_laplace_lik_check: n_data = %d", n_data);
+  DevBuf<double> d_D, d_Bx, d_dld, d_sv, d_yr, d_w, d_fe, d_rhs, d_dw, d_rdw, d_out2, d_each, d_dW3, d_gF, d_out3;
+  DevBuf<int> d_yi, d_ptr;
+  HIP_OK(up(d_D, D, n)); HIP_OK(up(d_dld, dld, n)); HIP_OK(up(d_sv, sv, n));
+  if (Bx) HIP_OK(up(d_Bx, Bx, n));
+  if (re_ptr) HIP_OK(up(d_ptr, re_ptr, (size_t)n + 1));
+  if (y_int) HIP_OK(up(d_yi, y_int, n_data)); else HIP_OK(up(d_yr, y_real, n_data));
+  if (weights) HIP_OK(up(d_w, weights, n_data));
+  if (fixed_effects) HIP_OK(up(d_fe, fixed_effects, n_data));
+  HIP_OK(nan_filled(d_rhs, n)); HIP_OK(nan_filled(d_dw, n)); HIP_OK(nan_filled(d_rdw, n)); HIP_OK(nan_filled(d_dW3, n));
+  HIP_OK(nan_filled(d_out2, 2)); HIP_OK(nan_filled(d_each, 2 * (size_t)std::max(n_each, 1))); HIP_OK(nan_filled(d_gF, n_data)); HIP_OK(nan_filled(d_out3, 3));
+  const gpb::LikResp y{ d_yi, d_yr, aux, d_w, aux2 };
+  hipStream_t st = nullptr;
+  HIP_OK(gpb::lap_newton_setup(lik, d_mode, y, d_fe, d_D, n, d_W, d_rhs, d_dw, d_rdw, st, d_ptr));
+  HIP_OK(gpb::lap_objective(lik, d_mode, y, d_fe, d_Bx, d_D, n, d_out2, st, d_ptr));
+  for (int i = 0; i < n_each; ++i) {
+    if (re_ptr) HIP_OK(gpb::lap_objective(lik, d_mode.p + i, y, d_fe, nullptr, d_D.p + i, 1, d_each.p + 2 * i, st, d_ptr.p + i));      // re_ptr holds absolute positions: the data stay where they are
+    else {
+      const gpb::LikResp yi{ d_yi ? d_yi.p + i : nullptr, d_yr ? d_yr.p + i : nullptr, aux, d_w ? d_w.p + i : nullptr, aux2 };
+      HIP_OK(gpb::lap_objective(lik, d_mode.p + i, yi, d_fe ? d_fe.p + i : nullptr, nullptr, d_D.p + i, 1, d_each.p + 2 * i, st, nullptr));
+    }
+  }
+  HIP_OK(gpb::lap_third_deriv(lik, d_mode, y, d_fe, n, d_dW3, st, d_ptr));
+  if (re_ptr) HIP_OK(gpb::lap_grad_F_map(lik, d_mode, y, d_fe, d_dld, d_dW3, d_sv, n, d_ptr, d_gF, st));
+  else HIP_OK(gpb::lap_grad_F(lik, d_mode, y, d_fe, d_dld, d_sv, n, d_gF, st));
+  if (gpb::lik_has_aux(lik)) HIP_OK(gpb::lap_aux_grad(lik, d_mode, y, d_fe, d_dld, d_dW3, d_sv, n, d_ptr, d_out3, st));
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(down(W, d_W, n)); HIP_OK(down(rhs, d_rhs, n)); HIP_OK(down(dw, d_dw, n)); HIP_OK(down(rdw, d_rdw, n)); HIP_OK(down(dW3, d_dW3, n));
+  HIP_OK(down(out2, d_out2, 2)); HIP_OK(down(gradF, d_gF, n_data)); HIP_OK(down(out3, d_out3, 3));
+  if (n_each > 0) {
+    std::vector<double> each(2 * (size_t)n_each);
+    HIP_OK(down(each.data(), d_each, each.size()));
+    for (int i = 0; i < n_each; ++i) ll_each[i] = each[2 * (size_t)i];
+  }
+  API_END();
+}
+
 namespace {
 enum : int { LAP_RESET_MODE = 1, LAP_KEEP_GRAD_STATE = 2 };
 

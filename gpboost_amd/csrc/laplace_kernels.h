@@ -101,5 +101,7 @@ hipError_t lap_pred_rhs(const int* nn_p, const double* A_p, const int* sigma, in
 hipError_t lap_pred_quad(const int* nn_p, const double* A_p, const int* sigma, const double* X, int n, int m, int row0, int n_rows, int cnt, int nc,
                          int diag_only, double* out, hipStream_t st);
 hipError_t lap_sums3(const double* rdw, const double* D, const double* dD, int n, double* out3, hipStream_t st);
+// test only: out = f(x) with the device's library function fn (0 exp, 1 log, 2 log1p, 3 erfc, 4 lgamma, 5 sqrt) as laplace_kernels.hip is compiled
+hipError_t lap_math_probe(int fn, const double* x, int n, double* out, hipStream_t st);
 
 }  // namespace gpb

@@ -1903,4 +1903,27 @@ hipError_t lap_sums3(const double* rdw, const double* D, const double* dD, int n
   return hipGetLastError();
 }
 
+// Test only (gpb_hip_laplace_lik_check, op 1): one library function of the likelihood kernels on a vector, compiled with this file's flags, so that a test can
+// measure what the device's exp / log / log1p / erfc / lgamma / sqrt return (fn = 0 .. 5 in that order) apart from the formulas built on them.
+__global__ void lap_math_probe_kernel(int fn, const double* __restrict__ x, int n, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double v = x[i];
+  double r;
+  switch (fn) {
+    case 0: r = exp(v); break;
+    case 1: r = log(v); break;
+    case 2: r = log1p(v); break;
+    case 3: r = erfc(v); break;
+    case 4: r = lgamma(v); break;
+    default: r = sqrt(v); break;
+  }
+  out[i] = r;
+}
+hipError_t lap_math_probe(int fn, const double* x, int n, double* out, hipStream_t st) {
+  if (fn < 0 || fn > 5) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lap_math_probe_kernel, GRID1(n), 0, st, fn, x, n, out);
+  return hipGetLastError();
+}
+
 }  // namespace gpb

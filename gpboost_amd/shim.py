@@ -561,6 +561,44 @@ def dense_spd_solve(M, rhs=None, sub0=None):
     return x, inv
 
 
+def laplace_lik_check(lik, mode, D, dld, sv, y_int=None, y_real=None, re_ptr=None, weights=None, fixed_effects=None, Bx=None, aux=1.0, aux2=2.0, n_each=0):
+    """The likelihood kernels of the Vecchia-Laplace path on the caller's data (gpb_hip_laplace_lik_check, op 0; test seam).  lik: a name of _LIKELIHOODS or an id;
+    mode, D, dld, sv (n) and Bx (n) or None; re_ptr (n + 1) or None; exactly one of y_int / y_real, weights and fixed_effects per datum.
+    -> dict: W, rhs, dw, rdw, dW3 (n), out2 (2), ll_each (n_each), gradF (n, or n_data with re_ptr), out3 (3)"""
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+    lid = _LIKELIHOODS[lik][0] if isinstance(lik, str) else int(lik)
+    mode, D, dld, sv, Bx, w, fe, yr = f64(mode), f64(D), f64(dld), f64(sv), f64(Bx), f64(weights), f64(fixed_effects), f64(y_real)
+    yi, ptr = i32(y_int), i32(re_ptr)
+    n = mode.shape[0]
+    assert (yi is None) != (yr is None)
+    n_data = (yi if yr is None else yr).shape[0]
+    assert ptr is None or ptr.shape == (n + 1,)
+    for v in (D, dld, sv, Bx):
+        assert v is None or v.shape == (n,)
+    for v in (w, fe):
+        assert v is None or v.shape == (n_data,)
+    r = {k: np.empty(n) for k in ("W", "rhs", "dw", "rdw", "dW3")}
+    r.update(out2=np.empty(2), ll_each=np.empty(int(n_each)), gradF=np.empty(n_data), out3=np.empty(3))
+    _shim_call(_lib().gpb_hip_laplace_lik_check(C.c_int(0), C.c_int(lid), C.c_int(n), C.c_int(n_data), _p(ptr, C.c_int32), _p(yi, C.c_int32), _p(yr), _p(w), _p(fe),
+                                                _p(mode), _p(D), _p(Bx), _p(dld), _p(sv), C.c_double(aux), C.c_double(aux2), C.c_int(int(n_each)), _p(r["W"]),
+                                                _p(r["rhs"]), _p(r["dw"]), _p(r["rdw"]), _p(r["out2"]), _p(r["ll_each"]), _p(r["dW3"]), _p(r["gradF"]), _p(r["out3"])))
+    return r
+
+
+_MATH_PROBE_FNS = ("exp", "log", "log1p", "erfc", "lgamma", "sqrt")
+
+
+def math_probe(fn, x):
+    """The device's library function fn (one of _MATH_PROBE_FNS) on the vector x, compiled as the likelihood kernels are (gpb_hip_laplace_lik_check, op 1; test seam)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    nul = C.POINTER(C.c_double)()
+    _shim_call(_lib().gpb_hip_laplace_lik_check(C.c_int(1), C.c_int(_MATH_PROBE_FNS.index(fn)), C.c_int(x.shape[0]), C.c_int(x.shape[0]), None, None, nul, nul, nul,
+                                                _p(x), nul, nul, nul, nul, C.c_double(0.0), C.c_double(0.0), C.c_int(0), _p(out), nul, nul, nul, nul, nul, nul, nul, nul))
+    return out
+
+
 class LocalGroup(object):
     """In-process group of `world` ranks (threads of this process; their handles may share one device): the second transport behind the
     library's collectives (gpb_hip_local_group_create).  `run(fn)` calls fn(rank) on one thread per rank and returns the results in rank

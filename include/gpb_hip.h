@@ -555,6 +555,19 @@ GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int
 GPB_HIP_EXPORT int gpb_hip_vecchia_laplace_ops_check(gpb_hip_vecchia_t* h, int32_t op, int32_t form, int32_t ncol, int32_t nc, int32_t prefill, const double* A,
                                                      const double* D, const double* W, const double* scale, const double* A2, const double* X, double* out,
                                                      double* out2, int32_t* info);
+/* Test entry: the likelihood kernels of the Vecchia-Laplace path on the caller's own data, without a handle.  The arrays are uploaded as they are and go through the
+ * launchers the model uses; the entry holds no formula.
+ *   op 0  likelihood `lik` (an id of gpb_hip_vecchia_laplace_set_likelihood) on n rows.  re_ptr (n + 1, rising from 0 to n_data) or NULL (one datum per row, n_data = n);
+ *         y_int or y_real (n_data, exactly one of them); weights, fixed_effects (n_data) or NULL; mode, D, dld, sv (n); Bx (n) or NULL; aux, aux2.
+ *         Newton set-up: W, rhs, dw, rdw (n).  Objective over all rows: out2 = { sum of the log-likelihood, sum Bx^2 / D }; ll_each (n_each <= n): the objective launched on
+ *         each of the first n_each rows alone.  dW3 (n): d information / d location.  gradF: the boosting gradient, per row (n) without re_ptr, per datum (n_data) with it.
+ *         out3: the three data sums of the gradient wrt the auxiliary parameters (NaN for a likelihood without any).  gradF with re_ptr and out3 read the dW3 of this call.
+ *   op 1  the device's library function lik = 0 exp, 1 log, 2 log1p, 3 erfc, 4 lgamma, 5 sqrt on mode (n) -> W (n), compiled as the likelihood kernels are; every other
+ *         pointer may be NULL. */
+GPB_HIP_EXPORT int gpb_hip_laplace_lik_check(int32_t op, int32_t lik, int32_t n, int32_t n_data, const int32_t* re_ptr, const int32_t* y_int, const double* y_real,
+                                             const double* weights, const double* fixed_effects, const double* mode, const double* D, const double* Bx, const double* dld,
+                                             const double* sv, double aux, double aux2, int32_t n_each, double* W, double* rhs, double* dw, double* rdw, double* out2,
+                                             double* ll_each, double* dW3, double* gradF, double* out3);
 
 /* ------------------------------------------------------------------------------------
  * Exact (dense) GP, Gaussian likelihood -- BASELINE config 1: replaces CalcSigmaComps / CalcZSigmaZt / CalcChol /

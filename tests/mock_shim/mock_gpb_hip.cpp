@@ -762,7 +762,7 @@ EXPORT int gpb_hip_vecchia_newton_leaf_values(gpb_hip_vecchia_t* h, const int32_
   return 0;
 }
 #define NOT_IN_MOCK(name) EXPORT int name() { return fail("mock shim (tests/mock_shim): " #name " is not restated on the CPU"); }
-NOT_IN_MOCK(gpb_hip_dense_cholesky_check) NOT_IN_MOCK(gpb_hip_vecchia_laplace_ops_check) NOT_IN_MOCK(gpb_hip_exact_create) NOT_IN_MOCK(gpb_hip_exact_fisher_std_errors) NOT_IN_MOCK(gpb_hip_exact_free) NOT_IN_MOCK(gpb_hip_exact_grad_terms)
+NOT_IN_MOCK(gpb_hip_dense_cholesky_check) NOT_IN_MOCK(gpb_hip_vecchia_laplace_ops_check) NOT_IN_MOCK(gpb_hip_laplace_lik_check)NOT_IN_MOCK(gpb_hip_exact_create) NOT_IN_MOCK(gpb_hip_exact_fisher_std_errors) NOT_IN_MOCK(gpb_hip_exact_free) NOT_IN_MOCK(gpb_hip_exact_grad_terms)
 NOT_IN_MOCK(gpb_hip_exact_nll_terms) NOT_IN_MOCK(gpb_hip_exact_predict) NOT_IN_MOCK(gpb_hip_exact_psi_inv_diag) NOT_IN_MOCK(gpb_hip_exact_set_y)
 NOT_IN_MOCK(gpb_hip_vecchia_fisher_std_errors) NOT_IN_MOCK(gpb_hip_vecchia_grad_terms_allreduce)
 NOT_IN_MOCK(gpb_hip_vecchia_nll_terms_allreduce)

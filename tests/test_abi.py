@@ -20,7 +20,7 @@ def test_headers_declare_something():
     assert len(_declared("gpb_hip.h", "GPB_HIP_EXPORT")) >= 20
     assert "GPB_EvalNegLogLikelihood" in _declared("gpboost_c_api_subset.h", "GPBOOST_C_EXPORT")
     assert {"gpb_hip_dense_cholesky_check", "gpb_hip_dense_spd_solve", "gpb_hip_lowrank_ops_check", "gpb_hip_vecchia_set_worker_cap",
-            "gpb_hip_vecchia_set_nugget_diag", "gpb_hip_vecchia_laplace_ops_check"} <= set(_declared("gpb_hip.h", "GPB_HIP_EXPORT"))
+            "gpb_hip_vecchia_set_nugget_diag", "gpb_hip_vecchia_laplace_ops_check", "gpb_hip_laplace_lik_check"} <= set(_declared("gpb_hip.h", "GPB_HIP_EXPORT"))
 
 
 def test_library_exports_every_declared_symbol(lib_built):
