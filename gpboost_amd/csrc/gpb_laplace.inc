@@ -16,6 +16,18 @@
 #include <chrono>
 #include <random>
 
+// LaplaceState::pc_type, cg_preconditioner_type of the iterative methods.  The values are the ABI of gpb_hip_vecchia_laplace_set_preconditioner.
+enum LapPc : int {
+  kPcVadu = 0,              // P = B^T (D^-1 + W) B, the (Sigma^-1 + W) form of the solves
+  kPcPivChol = 1,           // "pivoted_cholesky": P = W^-1 + L_k L_k^T, the (W^-1 + Sigma) form
+  kPcFitc = 2,              // "fitc": P = diag(W^-1 + Sigma_m[0][0] - ||V_i||^2) + C Sigma_m^-1 C', the (W^-1 + Sigma) form
+  kPcVecchiaResponse = 3,   // "vecchia_response": P^-1 = B_p' D_p^-1 B_p, the Vecchia factor of W^-1 + Sigma (evaluation only)
+  kPcVifdu = 4,             // "vifdu": full-scale Vecchia only, the (Sigma^-1 + W) form with Sigma^-1 = S - Q M^-1 Q'
+  kPcNone = 5               // "none": the same form without a preconditioner
+};
+inline bool pc_has_lowrank(int pc) { return pc == kPcPivChol || pc == kPcFitc; }             // holds the low-rank factor d_pcL; the only ones besides vadu the gradient is built for
+inline bool pc_vif_only(int pc) { return pc == kPcVifdu || pc == kPcNone; }                    // belongs to full-scale Vecchia handles only
+
 struct LaplaceState {
   int n = 0, m = 0, t = 0, p_max = 0, seed = 0;
   struct Tri {                    // one level-scheduled triangular solve in level order (laplace_kernels.h: LapTri)
@@ -70,7 +82,7 @@ struct LaplaceState {
   int syncfree = 5;
   double* h_o = nullptr;          // pinned mirror: [0..8) reductions, [8..8+t) residual norms
   bool has_mode = false;
-  // ---- gradient of the approximate marginal likelihood (laplace_grad_current) ----
+  // ---- gradient of the approximate marginal likelihood (gpb_laplace_grad.inc) ----
   double* d_gblk = nullptr;       // 2 blocks kept from the log-determinant's block CG: U = (Sigma^-1 + W)^-1 Z and PI_Z = P^-1 Z
   size_t gblk_cap = 0;
   double* d_gvec = nullptr;       // 6 n-vectors: previous mode, third derivatives, d logdet / d mode, implicit solve, SigmaI_deriv mode, dD (storage order)
@@ -78,10 +90,10 @@ struct LaplaceState {
   double* d_dD = nullptr;         // dD / d log(range), Vecchia order
   double* d_go = nullptr; double* h_go = nullptr; size_t go_cap = 0;   // column dot products of the trace estimators (device, pinned mirror)
   bool grad_state = false;        // U / PI_Z / the factor belong to the current mode and parameters
-  bool gvec_state = false;        // d logdet / d mode and the implicit solve (d_gvec) belong to them too (laplace_grad_current has run)
+  bool gvec_state = false;        // d logdet / d mode and the implicit solve (d_gvec) belong to them too (gpb_hip_vecchia_laplace_grad_current has run)
   int g_cov = 0, g_t = 0; double g_var = 0., g_a = 0.;
   // ---- cg_preconditioner_type = "pivoted_cholesky" (gpb_hip_vecchia_laplace_set_preconditioner; pivchol_kernels.hip) ----
-  int pc_type = 0;                // 0 = "vadu" (P = B^T (D^-1 + W) B, the (Sigma^-1 + W) form of the solves), 1 = "pivoted_cholesky" (P = W^-1 + L_k L_k^T, the (W^-1 + Sigma) form)
+  int pc_type = kPcVadu;          // a LapPc
   int pc_rank = 50;               // fitc_piv_chol_preconditioner_rank_ (re_model_template.h:5922 default_piv_chol_preconditioner_rank_)
   int pc_k = 0;                   // columns of L_k = min(rank, n)
   double* d_pcL = nullptr;        // L_k [n][pc_k], rows in storage order; renewed by every evaluation (the covariance parameters changed)
@@ -94,7 +106,7 @@ struct LaplaceState {
   double pc_logdet = 0.;          // log|I_k + L_k^T W L_k| of the last pc_refresh
   int pc_cols = 0;                // columns the last factorisation computed before its error bound was met
   int rv_pc = -1, rv_k = -1;      // preconditioner type / k the cached probe vectors were drawn for
-  // ---- cg_preconditioner_type = "fitc" (pc_type 2): P = diag(W^-1 + Sigma_m[0][0] - ||V_i||^2) + C Sigma_m^-1 C'; d_pcL holds C, the cross-covariance with the inducing points ----
+  // ---- cg_preconditioner_type = "fitc" (kPcFitc): P = diag(W^-1 + Sigma_m[0][0] - ||V_i||^2) + C Sigma_m^-1 C'; d_pcL holds C, the cross-covariance with the inducing points ----
   std::vector<double> pc_ip;      // inducing points, k x 3 row-major (unused coordinates 0; gpb_hip_vecchia_laplace_set_inducing_points)
   int pc_nip = 0;
   double* d_pcip = nullptr;       // the same on the device
@@ -106,8 +118,8 @@ struct LaplaceState {
   double* d_pcI = nullptr;        // k x k identity (multiplier of plain L' X reductions)
   std::vector<double> pc_Sm;      // Sigma_m with the jittered diagonal, k x k
   double pc_logdet_Sm = 0.;
-  const double* pc_wp(const double* W) const { return pc_type == 2 ? d_pcwp : W; }
-  // ---- cg_preconditioner_type = "vecchia_response" (pc_type 3): P^-1 = B_p' D_p^-1 B_p, the Vecchia factor of W^-1 + Sigma on the same neighbour sets, renewed for
+  const double* pc_wp(const double* W) const { return pc_type == kPcFitc ? d_pcwp : W; }
+  // ---- cg_preconditioner_type = "vecchia_response" (kPcVecchiaResponse): P^-1 = B_p' D_p^-1 B_p, the Vecchia factor of W^-1 + Sigma on the same neighbour sets, renewed for
   // every W by a MODE_FACTOR launch of the point kernel with the diagonal additions 1 / W_i (likelihoods.h:16315-16323; CalcVecchiaApproxLatentAddDiagonal) ----
   double* d_vrA = nullptr;        // A_p [n][m], Vecchia order
   double* d_vrD = nullptr;        // D_p (+ the jitter), Vecchia order; then [n] u (unused), [n] the nuggets 1 / W_i + jitter (Vecchia order)
@@ -129,11 +141,11 @@ struct LaplaceState {
   std::vector<double> vif_Sm, vif_Linv;   // Sigma_m (jittered diagonal) and the inverse of its Cholesky factor
   double vif_logdet_Sm = 0.;
   std::vector<double> vif_G;      // (B C)' D^-1 (B C), k x k row-major
-  // gradient (laplace_grad_current): storage-order copies [n][k] of C, dC / d log(range), B dC; the preconditioner's dC_p / d log(range); scratch
+  // gradient (gpb_laplace_grad.inc): storage-order copies [n][k] of C, dC / d log(range), B dC; the preconditioner's dC_p / d log(range); scratch
   double* d_vifC = nullptr; double* d_vifdC = nullptr; double* d_vifBdC = nullptr; double* d_pcdL = nullptr; double* d_vifT = nullptr; size_t vifT_cap = 0;
   double* d_vifq = nullptr; size_t vifq_cap = 0;      // small operands of the block reductions
   bool vif_grad_inputs = false;   // dC, B dC (and the preconditioner's dC_p) belong to the current parameters
-  // "vifdu" (pc_type 4) / "none" (pc_type 5): the (Sigma^-1 + W) form with Sigma^-1 = S - Q M^-1 Q' (CGFVIFLaplaceVec / CGTridiagVIFLaplace, CG_utils.cpp:501-742)
+  // "vifdu" (kPcVifdu) / "none" (kPcNone): the (Sigma^-1 + W) form with Sigma^-1 = S - Q M^-1 Q' (CGFVIFLaplaceVec / CGTridiagVIFLaplace, CG_utils.cpp:501-742)
   std::vector<double> vif_M;      // the Woodbury matrix M = Sigma_m + (B C)' D^-1 (B C), k x k row-major (its factor: vif_cholM)
   double* d_vifMinv = nullptr;    // M^-1, then (M - (D^-1 B C)' diag((W + D^-1)^-1) (D^-1 B C))^-1 ("vifdu", renewed for every W): 2 x k x k
   double* d_vifblk = nullptr; size_t vifblk_cap = 0;    // two block vectors + two n-vectors of scratch
@@ -610,13 +622,13 @@ int gpb_hip_vecchia_laplace_set_binomial(gpb_hip_vecchia_t* h, int on) {
 // inducing points, 3 = "vecchia_response" (rank unused; evaluation only -- the reference refuses the gradient with it, likelihoods.h:6570-6572).
 int gpb_hip_vecchia_laplace_set_preconditioner(gpb_hip_vecchia_t* h, int type, int rank) {
   if (!h) return fail("null argument");
-  if (type < 0 || type > 5) return fail("preconditioner type %d is not on this path (0 = vadu, 1 = pivoted_cholesky, 2 = fitc, 3 = vecchia_response; full-scale Vecchia: 2 = fitc, 4 = vifdu, 5 = none)", type);
-  if ((type == 4 || type == 5) && h->vif_k < 1) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
+  if (type < kPcVadu || type > kPcNone) return fail("preconditioner type %d is not on this path (0 = vadu, 1 = pivoted_cholesky, 2 = fitc, 3 = vecchia_response; full-scale Vecchia: 2 = fitc, 4 = vifdu, 5 = none)", type);
+  if (pc_vif_only(type) && h->vif_k < 1) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
   if (!h->lap) h->lap = new LaplaceState();
   LaplaceState* s = h->lap;
-  const int rk = rank > 0 ? rank : (type == 2 ? 200 : 50);            // default_fitc_preconditioner_rank_ / default_piv_chol_preconditioner_rank_ (re_model_template.h:5921-5922)
-  if (type == 1 && rk > h->n) return fail("'fitc_piv_chol_preconditioner_rank' cannot be larger than the dimension of the mode (= number of unique locations) ");   // likelihoods.h:936-938
-  if (type == 1 && rk > gpb::pc_max_rank)
+  const int rk = rank > 0 ? rank : (type == kPcFitc ? 200 : 50);            // default_fitc_preconditioner_rank_ / default_piv_chol_preconditioner_rank_ (re_model_template.h:5921-5922)
+  if (type == kPcPivChol && rk > h->n) return fail("'fitc_piv_chol_preconditioner_rank' cannot be larger than the dimension of the mode (= number of unique locations) ");   // likelihoods.h:936-938
+  if (type == kPcPivChol && rk > gpb::pc_max_rank)
     return fail("pivoted_cholesky preconditioner: at most %d columns on this path (the k x 4 operand of a probe chunk is kept in 64 KB of LDS; got fitc_piv_chol_preconditioner_rank = %d)", gpb::pc_max_rank, rk);
   if (s->pc_type != type || s->pc_rank != rk) { s->grad_state = false; s->gvec_state = false; }
   if (s->pc_type != type) {
@@ -963,7 +975,7 @@ int pc_factor_fitc(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double v
   return 0;
 }
 int pc_factor_sigma(gpb_hip_vecchia_t* h, LaplaceState* s, int cov_type, double var, double a, hipStream_t st) {
-  if (s->pc_type == 2) return pc_factor_fitc(h, s, cov_type, var, a, st);
+  if (s->pc_type == kPcFitc) return pc_factor_fitc(h, s, cov_type, var, a, st);
   const int n = h->n, k = std::min(s->pc_rank, n);
   if (h->d > 3) return fail("pivoted_cholesky preconditioner: coordinate dimensions 1..3 (this model has %d)", h->d);
   if (s->pc_k != k || !s->d_pcL || !s->d_pcdiag) {
@@ -1064,7 +1076,7 @@ int pc_refresh(LaplaceState* s, int n, const double* W, hipStream_t st, int* bad
   *bad = 0;
   const size_t need = (size_t)parts * npairs;
   if (s->pcpart_cap < need) { dev_free(s->d_pcpart); s->pcpart_cap = 0; HIP_OK(hipMalloc(&s->d_pcpart, sizeof(double) * need)); s->pcpart_cap = need; }
-  const bool fitc = s->pc_type == 2;
+  const bool fitc = s->pc_type == kPcFitc;
   double sum_log_wp = 0.0;
   if (fitc) {       // D^-1 for this W (likelihoods.h:16302-16308) and sum log D^-1 (the log|P| of :16465-16470)
     HIP_OK(gpb::pc_fitc_diag(W, s->d_pcvn2, s->pc_Sm[0], n, s->d_pcwp, st));
@@ -1148,7 +1160,7 @@ bool spd_invert(std::vector<double>& A, int k, double* logdet) {
 // the storage-order copies of V and B C, 1 / D, the small multipliers (after build_levels: needs sigma)
 int vif_lap_pack(gpb_hip_vecchia_t* h, LaplaceState* s, bool with_grad, hipStream_t st) {
   const int n = h->n, k = h->vif_k, kq = h->vif_kq;
-  if (s->pc_type >= 4 && !with_grad) {       // "vifdu" / "none": C in storage order (the preconditioner, the probes)
+  if (pc_vif_only(s->pc_type) && !with_grad) {       // "vifdu" / "none": C in storage order (the preconditioner, the probes)
     if (!s->d_vifC || s->vif_kk != k) { dev_free(s->d_vifC); HIP_OK(hipMalloc(&s->d_vifC, sizeof(double) * (size_t)n * k)); }
     HIP_OK(gpb::pc_pack_rows(h->d_vC, kq, s->d_sigma, n, k, s->d_vifC, nullptr, st));
   }
@@ -1273,7 +1285,7 @@ int lap_fetch(LaplaceState* s, int count, hipStream_t st) {      // d_o[0..count
 //   kVifSigmaInv      the same with Sigma^-1 = S - Q M^-1 Q' (full-scale Vecchia), P of "vifdu" or the identity ("none")
 //   kWinvPlusSigma    (W^-1 + Sigma) x,   P of pivoted_cholesky / fitc / vecchia_response (Sigma with its low-rank part for full-scale Vecchia)
 enum class LapForm { kVadu, kVifSigmaInv, kWinvPlusSigma };
-LapForm lap_form(const LaplaceState* s) { return s->pc_type == 0 ? LapForm::kVadu : (s->pc_type >= 4 ? LapForm::kVifSigmaInv : LapForm::kWinvPlusSigma); }
+LapForm lap_form(const LaplaceState* s) { return s->pc_type == kPcVadu ? LapForm::kVadu : (pc_vif_only(s->pc_type) ? LapForm::kVifSigmaInv : LapForm::kWinvPlusSigma); }
 // scratch of the operand's shape: ap for apply, pc for precond, x1 / x2 for the Woodbury parts of either (kVifSigmaInv only)
 struct LapScratch { double *ap, *pc, *x1, *x2; };
 struct LapSolver {
@@ -1320,14 +1332,14 @@ struct LapSolver {
       case LapForm::kVifSigmaInv:
         return vif_precond(r, z, t.pc, t.x1, t.x2, ncol, nc);
       case LapForm::kWinvPlusSigma:
-        return s->pc_type == 3 ? pc_apply_vr(h, s, r, z, ncol, nc, st) : pc_apply(s, n, W, r, z, ncol, nc, 0, st);
+        return s->pc_type == kPcVecchiaResponse ? pc_apply_vr(h, s, r, z, ncol, nc, st) : pc_apply(s, n, W, r, z, ncol, nc, 0, st);
     }
     return fail("internal: solver form");
   }
   // "none" the identity; "vifdu" B^-1 [x + (W + D^-1)^-1 D^-1 B C MM^-1 C' B' D^-1 x], x = (W + D^-1)^-1 B^-T rr (CG_utils.cpp:539-543)
   int vif_precond(const double* rr, double* zz, double* tt, double* tA, double* tB, int ncol, int nc) const {
     const int vk = h->vif_k;
-    if (s->pc_type == 5) { HIP_OK(hipMemcpyAsync(zz, rr, sizeof(double) * (size_t)n * ncol * nc, hipMemcpyDeviceToDevice, st)); return 0; }
+    if (s->pc_type == kPcNone) { HIP_OK(hipMemcpyAsync(zz, rr, sizeof(double) * (size_t)n * ncol * nc, hipMemcpyDeviceToDevice, st)); return 0; }
     HIP_OK(gpb::lap_vadu(lv, n, rdw, rr, zz, tt, ncol, nc, st));                                               // tt = B^-T rr, zz = B^-1 x
     HIP_OK(gpb::pc_rowscale(tt, vwdd, n, ncol, nc, 0, tA, st));                                                // D^-1 x
     HIP_OK(gpb::lap_Bt(lv, n, tA, tB, ncol, nc, st));
@@ -1358,7 +1370,7 @@ struct LapSolver {
     return 0;
   }
   // the preconditioner of the (W^-1 + Sigma) form for this W
-  int pc_renew(int* pbad, bool for_logdet) const { return s->pc_type == 3 ? pc_refresh_vr(h, s, W, st, pbad, for_logdet) : pc_refresh(s, n, W, st, pbad); }
+  int pc_renew(int* pbad, bool for_logdet) const { return s->pc_type == kPcVecchiaResponse ? pc_refresh_vr(h, s, W, st, pbad, for_logdet) : pc_refresh(s, n, W, st, pbad); }
 };
 LapSolver lap_solver(gpb_hip_vecchia_t* h, LaplaceState* s, const LapWork& w, LapForm form) {
   const int n = h->n;
@@ -1423,11 +1435,11 @@ int lap_eval_factor(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e)
   hipStream_t st = h->stream;
   if (alloc_factor(h)) return -1;
   if (h->vif_k > 0) {       // gp_approx = "full_scale_vecchia": Sigma = V V' + B^-1 D B^-T (FindModePostRandEffCalcMLLFSVA, likelihoods.h:3379-3750)
-    if (s->pc_type != 2 && s->pc_type != 4 && s->pc_type != 5) return fail("full-scale Vecchia with a non-Gaussian likelihood: cg_preconditioner_type must be 'fitc' (the reference's default), 'vifdu' or 'none'");
+    if (s->pc_type != kPcFitc && !pc_vif_only(s->pc_type)) return fail("full-scale Vecchia with a non-Gaussian likelihood: cg_preconditioner_type must be 'fitc' (the reference's default), 'vifdu' or 'none'");
     if (!s->re_ptr.empty()) return fail("full-scale Vecchia with a non-Gaussian likelihood: repeated locations are not on the HIP hot path");
-    return vif_lap_factor(h, s, e.cov_type, e.var, e.a, e.keep && s->pc_type == 2);
+    return vif_lap_factor(h, s, e.cov_type, e.var, e.a, e.keep && s->pc_type == kPcFitc);
   }
-  if (s->pc_type >= 4) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
+  if (pc_vif_only(s->pc_type)) return fail("the 'vifdu' / 'none' preconditioners belong to gp_approx = 'full_scale_vecchia'");
   if (lap_launch_factor(h, e.cov_type, e.var, e.a, 0)) return -1;
   HIP_OK(hipStreamSynchronize(st));
   h->has_factor = true;
@@ -1539,7 +1551,7 @@ int lap_eval_upload(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e)
   }
   if (!s->d_Ds) HIP_OK(hipMalloc(&s->d_Ds, sizeof(double) * (size_t)n));
   HIP_OK(gpb::lap_scatter(h->d_D, s->d_sigma, n, s->d_Ds, st));
-  if (h->vif_k > 0 && vif_lap_pack(h, s, e.keep && s->pc_type == 2, st)) return -1;
+  if (h->vif_k > 0 && vif_lap_pack(h, s, e.keep && s->pc_type == kPcFitc, st)) return -1;
   return 0;
 }
 // Probe columns N(0,1) in the layout [chunk][row][NCB]: column c from mt19937(seed_seq{seed, counter, 0, c}) (GenRandVecNormalParallel with run id `counter`), element i
@@ -1577,8 +1589,8 @@ int lap_eval_workspace(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs&
   }
   const bool vif = h->vif_k > 0;
   const bool pc = lap_form(s) == LapForm::kWinvPlusSigma;
-  const bool vifdu = s->pc_type == 4, fitc = s->pc_type == 2;
-  const bool vr = s->pc_type == 3;                    // no low-rank part: no second set of normals, the probes are drawn with generator counter 0 (likelihoods.h:3993-4009)
+  const bool vifdu = s->pc_type == kPcVifdu, fitc = s->pc_type == kPcFitc;
+  const bool vr = s->pc_type == kPcVecchiaResponse;                    // no low-rank part: no second set of normals, the probes are drawn with generator counter 0 (likelihoods.h:3993-4009)
   if (vr) { s->vr_cov = e.cov_type; s->vr_var = e.var; s->vr_a = e.a; }
   if (fitc && s->pc_nip < 1) return fail("the fitc preconditioner needs its inducing points (gpb_hip_vecchia_laplace_set_inducing_points)");
   const int pck = fitc ? s->pc_nip : ((pc && !vr) ? std::min(s->pc_rank, n) : (vifdu ? h->vif_k : 0));
@@ -1620,7 +1632,7 @@ int lap_eval_operators(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs&
     HIP_OK(gpb::lap_permute_factor(h->d_A, tr->hpos, tr->opos, (size_t)tr->nslots * 32, tr->novf, tr->hent, tr->oent, st));
   HIP_OK(gpb::lap_dense_build(lv.fdense, h->d_A, st));
   HIP_OK(gpb::lap_dense_build(lv.bdense, h->d_A, st));
-  if ((s->pc_type == 1 || s->pc_type == 2) && pc_factor_sigma(h, s, e.cov_type, e.var, e.a, st)) return -1;
+  if (pc_has_lowrank(s->pc_type) && pc_factor_sigma(h, s, e.cov_type, e.var, e.a, st)) return -1;
   if (lap_form(s) == LapForm::kVifSigmaInv) {
     const int vk = h->vif_k;
     const size_t need = (size_t)2 * w.nb + (size_t)2 * n;      // (LapSolver: vblkA, vblkB, vwdd, vwgt)
@@ -1674,7 +1686,7 @@ int lap_find_mode(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e, c
         if (lap_fetch(s, 1, st)) return -1;
         if (!(s->h_o[0] <= 1e10)) { bad = true; break; }
         int pbad = 0;
-        if (pc ? op.pc_renew(&pbad, false) : (s->pc_type == 4 && op.vifdu_refresh(&pbad))) return -1;
+        if (pc ? op.pc_renew(&pbad, false) : (s->pc_type == kPcVifdu && op.vifdu_refresh(&pbad))) return -1;
         if (pbad) { bad = true; break; }
       }
       if (pc) {
@@ -1755,7 +1767,7 @@ int lap_logdet(gpb_hip_vecchia_t* h, LaplaceState* s, const LapEvalArgs& e, cons
   const gpb::LapLevels& lv = op.lv;
   const double* Ds = s->d_Ds;
   const bool vif = op.vif, pc = op.form == LapForm::kWinvPlusSigma, vsi = op.form == LapForm::kVifSigmaInv;
-  const bool fitc = s->pc_type == 2, vr = s->pc_type == 3, vifdu = s->pc_type == 4;
+  const bool fitc = s->pc_type == kPcFitc, vr = s->pc_type == kPcVecchiaResponse, vifdu = s->pc_type == kPcVifdu;
   double *R = w.R, *Z = w.Z, *H = w.H, *Vb = w.Vb, *T = w.T;
   const LapScratch scr{ T, T, op.vblkA, op.vblkB };
   auto lost = [&](int k_done) { out9_host[0] = NAN; out9_host[3] = NAN; out9_host[4] = k_done; };
@@ -2048,300 +2060,6 @@ int vif_grad_vec_sums(gpb_hip_vecchia_t* h, LaplaceState* s, VifGradHost* vg, co
   HIP_OK(gpb::pc_ltwx(s->d_vifdC, s->d_vifones, Ik, Q4, n, k, 4, 1, s->d_pcpart, s->d_vifx2, st));
   HIP_OK(hipMemcpyAsync(vg->ydC.data(), s->d_vifx2, sizeof(double) * (size_t)4 * k, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  return 0;
-}
-// parameter j (0: log variance, 1: log range): -> d(-mll) / d theta_j;  z1[c] = (Sigma_v U_c)' SigmaI_deriv (Sigma_v P^-1 Z_c) from the Vecchia path's block products,
-// mSm0 / sSm0 = mode' S_deriv mode, sv' S_deriv mode.  parts4 = { mode' SigmaI_deriv_mode, d logdet / d theta_j, optimal c, implicit part }
-double vif_grad_assemble(const LaplaceState* s, const VifGradHost& vg, int j, int t, int tc, const double* z1, double mSm0, double sSm0, double* parts4) {
-  const int k = vg.k, kp = vg.kp, nc = 4;
-  auto dot = [](const double* a, const double* b, int kk) { double r = 0.0; for (int i = 0; i < kk; ++i) r += a[i] * b[i]; return r; };
-  auto matvec = [](const std::vector<double>& M, const double* x, int kk, double* out) { for (int i = 0; i < kk; ++i) { double r = 0.0; for (int p = 0; p < kk; ++p) r += M[(size_t)i * kk + p] * x[p]; out[i] = r; } };
-  // ---- x' SigmaI_deriv_mode for x = mode, sv ----
-  const double* yC = vg.yC.data(); const double* ydC = (j == 0) ? vg.yC.data() : vg.ydC.data();
-  const int a1col = (j == 0) ? 0 : 2;
-  std::vector<double> wsol(k), kv(k), Mgw(k);
-  for (int q = 0; q < k; ++q) wsol[q] = -yC[q];                                 // C' S mode
-  sm::cholesky_solve(s->vif_cholM.data(), k, k, wsol.data());
-  matvec(vg.Mg[j], wsol.data(), k, Mgw.data());
-  for (int q = 0; q < k; ++q) kv[q] = yC[(size_t)a1col * k + q] + (-ydC[q]) - Mgw[q];        // C' a1 + dC' S mode - Mg wsol
-  sm::cholesky_solve(s->vif_cholM.data(), k, k, kv.data());
-  double val[2];
-  for (int x = 0; x < 2; ++x) {
-    const double xa1 = x == 0 ? mSm0 : sSm0;
-    const double* CtSIdx = yC + (size_t)((j == 0) ? x : 2 + x) * k;
-    const double* CtS0x = yC + (size_t)x * k;                                   // = -C' S x
-    const double* dCtS0x = ydC + (size_t)x * k;                                 // = -dC' S x
-    val[x] = xa1 - dot(CtSIdx, wsol.data(), k) + dot(CtS0x, kv.data(), k) + dot(dCtS0x, wsol.data(), k);
-  }
-  const double mSm = val[0], sSm = val[1];
-  // ---- stochastic trace with the preconditioner's control variate ----
-  std::vector<double> sS(t), sP(t), cu(k), dcu(k), cp(k), dcp(k), sicu(k), sicp(k), tv(k), cpp(kp), dcpp(kp), s1(kp), tvp(kp);
-  const std::vector<double>& dCUv = (j == 0) ? vg.CU : vg.dCU;
-  const std::vector<double>& dCPv = (j == 0) ? vg.CP : vg.dCP;
-  const std::vector<double>& dCpPv = (j == 0) ? vg.CpP : vg.dCpP;
-  double mS = 0.0, mP = 0.0;
-  for (int c = 0; c < t; ++c) {
-    const int ch = c / nc, cc = c % nc;
-    for (int q = 0; q < k; ++q) {
-      const size_t o = ((size_t)ch * k + q) * nc + cc;
-      cu[q] = vg.CU[o]; dcu[q] = dCUv[o]; cp[q] = vg.CP[o]; dcp[q] = dCPv[o];
-    }
-    apply_linv_sym(s->vif_Linv, k, cu.data(), sicu.data());
-    apply_linv_sym(s->vif_Linv, k, cp.data(), sicp.data());
-    matvec(vg.dSm[j], sicp.data(), k, tv.data());
-    const double part1 = dot(dcu.data(), sicp.data(), k) + dot(sicu.data(), dcp.data(), k) - dot(sicu.data(), tv.data(), k);
-    sS[c] = part1 - z1[c];
-    for (int q = 0; q < kp; ++q) { const size_t o = ((size_t)ch * kp + q) * nc + cc; cpp[q] = vg.CpP[o]; dcpp[q] = dCpPv[o]; }
-    apply_linv_sym(s->pc_Linv, kp, cpp.data(), s1.data());
-    matvec(vg.dSmp[j], s1.data(), kp, tvp.data());
-    sP[c] = 2.0 * dot(dcpp.data(), s1.data(), kp) - dot(s1.data(), tvp.data(), kp) + vg.wn[j][c];
-    mS += sS[c]; mP += sP[c];
-  }
-  mS /= t; mP /= t;
-  // deterministic tr(P^-1 dP): sum dgrad wp - tr(Sigma_m,p^-1 dSigma_m,p) + tr(M_p^-1 sigma_woodbury_grad_preconditioner)
-  double tr = vg.sum_dgrad_wp[j];
-  {
-    std::vector<double> col(kp), out(kp);
-    for (int c = 0; c < kp; ++c) {
-      for (int q = 0; q < kp; ++q) col[q] = vg.dSmp[j][(size_t)q * kp + c];
-      apply_linv_sym(s->pc_Linv, kp, col.data(), out.data());
-      tr -= out[c];
-    }
-    for (int i = 0; i < kp; ++i) for (int p = 0; p < kp; ++p) tr += s->pc_Minv[(size_t)i * kp + p] * vg.Mgp[j][(size_t)p * kp + i];
-  }
-  double cov = 0.0, var = 0.0;
-  for (int c = 0; c < t; ++c) { cov += (sS[c] - mS) * (sP[c] - tr); var += (sP[c] - tr) * (sP[c] - tr); }
-  cov /= t; var /= t;
-  const double copt = (var == 0.0) ? 1.0 : cov / var;
-  const double dl = mS - copt * (mP - tr);
-  (void)tc;
-  parts4[0] = mSm; parts4[1] = dl; parts4[2] = copt; parts4[3] = -sSm;
-  return 0.5 * (mSm + dl) - sSm;
-}
-
-// Gradient of the NEGATIVE approximate marginal log-likelihood wrt (log sigma1^2, log a) at the state the last laplace_eval(...,
-// LAP_KEEP_GRAD_STATE) left behind: the mode, the factor, W / dw / rdw at the mode, U and PI_Z of the log-determinant's block CG.
-//   Likelihood::CalcGradNegMargLikelihoodLaplaceApproxVecchia   include/GPBoost/likelihoods.h:6521-6700
-//   CalcLogDetStochDerivModeVecchia / ...CovParVecchia (vadu)   :16636-16690, :16706-16790
-//   CalcOptimalC / CalcOptimalCVectorized                       src/GPBoost/CG_utils.cpp:1053-1090
-// Checker: oracle/gpb_oracle.c orc_vecchia_laplace_grad (same steps, same names).  parts_host (optional, 8 doubles): per parameter
-// { mode' SigmaI_deriv mode, d logdet / d theta, optimal c, implicit part }; vecs_host (optional, 2 n doubles, Vecchia order):
-// d logdet / d mode and (Sigma^-1 + W)^-1 d_mll_d_mode -- the intermediate values the step-wise parity tests compare.
-int laplace_grad_current(gpb_hip_vecchia_t* h, int cg_max_num_it, double cg_delta_conv, double* grad2_host, double* parts_host, double* vecs_host) {
-  if (!h || !grad2_host) return fail("null argument");
-  LaplaceState* s = h->lap;
-  if (s && s->pc_type == 3) return fail("Calculation of gradients is currently not correctly implemented for the '%s' preconditioner ", "vecchia_response");   // likelihoods.h:6570-6572
-  if (s && h->vif_k > 0 && s->pc_type != 2) return fail("full-scale Vecchia with a non-Gaussian likelihood: the gradient is built for the fitc preconditioner (the reference's default); '%s' serves evaluations and Nelder-Mead fits", s->pc_type == 4 ? "vifdu" : "none");
-  if (!s || !s->grad_state || !s->d_gblk) return fail("the gradient needs the state of an evaluation that kept it (gpb_hip_vecchia_laplace_eval with keep_grad_state)");
-  if (cg_max_num_it < 1) return fail("cg_max_num_it must be positive");
-  HIP_OK(hipSetDevice(h->device));
-  const int n = h->n, m = h->m, t = s->g_t;
-  hipStream_t st = h->stream;
-  const LapWork w = lap_work(h, s, t);
-  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
-  const size_t nb = w.nb, vb = w.vb;
-  double *mode = w.mode, *W = w.W, *rhs = w.rhs, *upd = w.upd, *mnew = w.mnew, *Bm = w.Bm, *dir = w.dir, *gv = w.gv, *r = w.r, *z = w.z, *hh = w.hh, *v = w.v,
-         *t1 = w.t1, *t2 = w.t2, *rdw = w.rdw;
-  double *dW3 = w.dW3, *dld = w.dld, *sv = w.sv, *SdM = w.SdM, *dDs = w.dDs;
-  double *R = w.R, *Z = w.Z, *H = w.H, *Vb = w.Vb, *T = w.T;      // free after the log-determinant
-  const double *U = s->d_gblk, *PIZ = s->d_gblk + nb;
-  const double* Ds = s->d_Ds;
-  const double* fe = s->has_fe ? s->d_fe : nullptr;
-  const LapSolver op = lap_solver(h, s, w, lap_form(s));
-  const gpb::LapLevels& lv = op.lv;
-  const size_t go_need = (size_t)10 * tc + 6;
-  if (s->go_cap < go_need) {
-    dev_free(s->d_go);
-    if (s->h_go) { (void)hipHostFree(s->h_go); s->h_go = nullptr; }
-    s->go_cap = 0;
-    HIP_OK(hipMalloc(&s->d_go, sizeof(double) * go_need));
-    HIP_OK(hipHostMalloc(&s->h_go, sizeof(double) * go_need));
-    s->go_cap = go_need;
-  }
-  double* go = s->d_go;
-  double* gov = go + (size_t)10 * tc;
-
-  const bool pc = s->pc_type >= 1;
-  const bool fitc = s->pc_type == 2;
-  const bool vif = h->vif_k > 0;
-  if (vif && (!fitc || !s->vif_grad_inputs || !s->d_pcdL)) return fail("full-scale Vecchia: the gradient needs an evaluation with the fitc preconditioner that kept its state");
-  if (pc && (s->gblk_cap < 4 * nb || !s->d_pcL || !s->d_pcM)) return fail("the gradient needs an evaluation with the pivoted_cholesky / fitc preconditioner that kept its state");
-  // ---- d log|Sigma W + I| / d mode (:16660-16688) ----
-  HIP_OK(gpb::lap_third_deriv(s->link, mode, s->resp(), fe, n, dW3, st, s->d_dptr));
-  if (pc) {
-    // pivoted_cholesky (:16554-16611): U = (W^-1 + Sigma)^-1 Z, PIZ = the probes Z themselves; W^-1 P^-1 Z = Z - L_k (I_k + L_k' W L_k)^-1 L_k' W Z -> R
-    if (fitc) {      // W^-1 P^-1 Z = W^-1 .* (D^-1 Z - D^-1 C M C' D^-1 Z)  (:16576-16583)
-      if (pc_apply(s, n, W, PIZ, R, tch, NCB, 0, st)) return -1;
-      HIP_OK(gpb::pc_rowscale(R, W, n, tch, NCB, 1, R, st));
-    } else if (pc_apply(s, n, W, PIZ, R, tch, NCB, 1, st)) return -1;
-    HIP_OK(gpb::pc_row_stats(U, R, s->d_pcL, s->d_pcM, W, dW3, n, s->pc_k, t, NCB, dld, st, fitc ? s->d_pcwp : nullptr, vif ? 1 : 0, v));
-  } else {
-  HIP_OK(gpb::lap_B(lv, n, PIZ, R, tch, NCB, st));                                   // B PI_Z
-  HIP_OK(gpb::lap_row_stats(U, PIZ, R, dW3, rdw, n, t, NCB, dld, st));
-  }
-  // ---- implicit part: (Sigma^-1 + W)^-1 d_mll_d_mode, d_mll_d_mode = 0.5 d logdet / d mode (:6599-6608; CGVecchiaLaplaceVec from 0) ----
-  HIP_OK(gpb::lap_lincomb(rhs, dld, dld, 0.5, 0.0, n, st));
-  HIP_OK(gpb::lap_dot(rhs, rhs, n, s->d_o, st));
-  HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipMemsetAsync(sv, 0, vb, st));
-  if (!(s->h_o[1] < 1e-100)) {
-    // vadu: CGVecchiaLaplaceVec from zero; otherwise Inv_SigmaI_plus_ZtWZ_Vecchia_iterative_given_PC -> CGVecchiaLaplace_Version_SigmaPlusWinvVec from zero with the
-    // preconditioner of the mode: (W^-1 + Sigma) u' = Sigma rhs, u = W^-1 u'
-    const LapScratch scr{ t1, t2, nullptr, nullptr };
-    if (pc) { if (op.sigma(rhs, r, t2, 1, 1)) return -1; }
-    else HIP_OK(hipMemcpyAsync(r, rhs, vb, hipMemcpyDeviceToDevice, st));
-    if (op.precond(r, z, scr, 1, 1)) return -1;
-    HIP_OK(hipMemcpyAsync(hh, z, vb, hipMemcpyDeviceToDevice, st));
-    int ncg = 0;
-    const int end = lap_cg(op, scr, sv, r, z, hh, v, 1, 1, w.sc1, LapCgRule{ std::min(cg_max_num_it, n), cg_delta_conv, 1, false, 1, false }, &ncg);
-    if (end == LAP_CG_ERROR) return -1;
-    if (end == LAP_CG_NONFINITE) return fail("NaN or Inf occurred in the conjugate gradient algorithm (implicit derivative)");
-    if (pc) HIP_OK(gpb::pc_rowscale(sv, W, n, 1, 1, 1, sv, st));
-  }
-  // ---- dA, dD wrt the log range; their entries in the two level-ordered layouts ----
-  if (!s->d_dA) {
-    HIP_OK(hipMalloc(&s->d_dA, sizeof(double) * (size_t)n * m));
-    HIP_OK(hipMalloc(&s->d_dD, sizeof(double) * (size_t)n));
-  }
-  if (m > 126) return fail("gradient of the Laplace approximation: the per-point derivative kernel handles at most 126 neighbours (this model has %d)", m);
-  if (h->d > 3) return fail("gradient of the Laplace approximation: the per-point derivative kernel handles coordinate dimensions 1..3 (this model has %d)", h->d);
-  VifGradHost vg;
-  if (vif) {
-    if (vif_grad_prepare(h, s, &vg, st)) return -1;              // dA / dD of the residual process wrt log(range) into d_dA / d_dD, the k x k matrices of the host half
-  } else
-  HIP_OK(gpb::lap_range_deriv(h->d_pts, h->d_nn, h->d_A, n, m, s->g_cov, h->d == 3 ? 1 : 0, s->g_var, s->g_a, s->d_dA, s->d_dD, st));
-  HIP_OK(gpb::lap_scatter(s->d_dD, s->d_sigma, n, dDs, st));
-  for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd }) {
-    const size_t nh = (size_t)tr->nslots * 32, no = tr->novf > 0 ? tr->novf : 1;
-    if (!tr->hent_g) {                          // same sources as the solve's own entries; the coefficients are refreshed below
-      HIP_OK(hipMalloc(&tr->hent_g, sizeof(gpb::LapEnt) * nh));
-      HIP_OK(hipMalloc(&tr->oent_g, sizeof(gpb::LapEnt) * no));
-      HIP_OK(hipMemcpyAsync(tr->hent_g, tr->hent, sizeof(gpb::LapEnt) * nh, hipMemcpyDeviceToDevice, st));
-      HIP_OK(hipMemcpyAsync(tr->oent_g, tr->oent, sizeof(gpb::LapEnt) * no, hipMemcpyDeviceToDevice, st));
-    }
-    HIP_OK(gpb::lap_permute_factor(s->d_dA, tr->hpos, tr->opos, nh, tr->novf, tr->hent_g, tr->oent_g, st));
-  }
-  gpb::LapTri fwd_g = lv.fwd, bwd_g = lv.bwd;
-  fwd_g.hent = s->fwd.hent_g; fwd_g.oent = s->fwd.oent_g;
-  bwd_g.hent = s->bwd.hent_g; bwd_g.oent = s->bwd.oent_g;
-  HIP_OK(gpb::lap_sums3(rdw, Ds, dDs, n, s->d_o + 4, st));
-  const double* nul = nullptr;
-  // ---- variance: SigmaI_deriv = -Sigma^-1 (:6613-6620), P_deriv = SigmaI_deriv ----
-  HIP_OK(gpb::lap_B(lv, n, mode, Bm, 1, 1, st));
-  HIP_OK(gpb::lap_deriv_mid(Bm, nul, Ds, nul, nul, n, 1, 1, 0, dir, nullptr, st));
-  HIP_OK(gpb::lap_Bt(lv, n, dir, SdM, 1, 1, st));
-  HIP_OK(gpb::lap_coldots(mode, sv, SdM, n, 1, 1, gov, st));
-  // the block operands of the trace estimators: vadu U, PI_Z (R = B PI_Z from above); pivoted_cholesky (CalcLogDetStochDerivCovParVecchia :16716-16735)
-  // Sigma U and Sigma (W W^-1 P^-1 Z), no control variate
-  const double *Ub = U, *Pb = PIZ;
-  if (pc) {
-    double *SU = s->d_gblk + 2 * nb, *SPZ = s->d_gblk + 3 * nb;
-    HIP_OK(gpb::pc_rowscale(R, W, n, tch, NCB, 0, Z, st));                           // P^-1 Z = W .* (W^-1 P^-1 Z)
-    if (vif && vif_grad_block_sums(h, s, &vg, U, Z, T, dDs, tch, NCB, st)) return -1;   // the k-vectors C' U_c, dC' U_c, ... of the host half; the control variate's diagonal parts
-    HIP_OK(gpb::lap_vadu(lv, n, Ds, Z, SPZ, T, tch, NCB, st));
-    HIP_OK(gpb::lap_vadu(lv, n, Ds, U, SU, T, tch, NCB, st));
-    HIP_OK(gpb::lap_B(lv, n, SPZ, R, tch, NCB, st));
-    Ub = SU; Pb = SPZ;
-  }
-  HIP_OK(gpb::lap_deriv_mid(R, nul, Ds, nul, nul, n, tch, NCB, 0, H, nullptr, st));
-  HIP_OK(gpb::lap_Bt(lv, n, H, T, tch, NCB, st));
-  HIP_OK(gpb::lap_coldots(Ub, Pb, T, n, tch, NCB, go, st));
-  // ---- range: SigmaI_deriv = B_grad' D^-1 B + B' D^-1 B_grad - B' D^-1 D_grad D^-1 B, B_grad = -dA (:6621-6640);
-  //      P_deriv = SigmaI_deriv + B' W B_grad + B_grad' W B (:16760-16775) ----
-  HIP_OK(gpb::lap_mul(fwd_g, n, mode, gv, 1, 1, st));
-  HIP_OK(gpb::lap_deriv_mid(Bm, gv, Ds, dDs, W, n, 1, 1, 1, dir, mnew, st));
-  HIP_OK(gpb::lap_Bt(lv, n, dir, upd, 1, 1, st));
-  HIP_OK(gpb::lap_coldots(mode, sv, upd, n, 1, 1, gov + 2, st));
-  HIP_OK(gpb::lap_mul(bwd_g, n, mnew, t1, 1, 1, st));
-  HIP_OK(gpb::lap_coldots(mode, sv, t1, n, 1, 1, gov + 4, st));
-  HIP_OK(gpb::lap_mul(fwd_g, n, Pb, Z, tch, NCB, st));
-  HIP_OK(gpb::lap_deriv_mid(R, Z, Ds, dDs, W, n, tch, NCB, 1, H, Vb, st));
-  HIP_OK(gpb::lap_Bt(lv, n, H, T, tch, NCB, st));
-  HIP_OK(gpb::lap_coldots(Ub, Pb, T, n, tch, NCB, go + (size_t)2 * tc, st));
-  HIP_OK(gpb::lap_mul(bwd_g, n, Vb, T, tch, NCB, st));
-  HIP_OK(gpb::lap_coldots(Ub, Pb, T, n, tch, NCB, go + (size_t)4 * tc, st));
-  if (!pc) {
-  HIP_OK(gpb::lap_deriv_mid(R, Z, Ds, dDs, W, n, tch, NCB, 2, H, Vb, st));
-  HIP_OK(gpb::lap_Bt(lv, n, H, T, tch, NCB, st));
-  HIP_OK(gpb::lap_coldots(U, PIZ, T, n, tch, NCB, go + (size_t)6 * tc, st));
-  HIP_OK(gpb::lap_mul(bwd_g, n, Vb, T, tch, NCB, st));
-  HIP_OK(gpb::lap_coldots(U, PIZ, T, n, tch, NCB, go + (size_t)8 * tc, st));
-  } else HIP_OK(hipMemsetAsync(go + (size_t)6 * tc, 0, sizeof(double) * (size_t)4 * tc, st));
-  if (vif) {
-    // S0 x = -Sigma_v^-1 x and S1 x = SigmaI_deriv(range) x for x = mode, sv -> the four columns r, z, hh, v (consecutive n-vectors); their products with C' and dC'
-    double* Q4 = r;
-    const double* xs[2] = { mode, sv };
-    for (int q = 0; q < 2; ++q) {
-      double* S0 = Q4 + (size_t)q * n; double* S1 = Q4 + (size_t)(2 + q) * n;
-      HIP_OK(gpb::lap_B(lv, n, xs[q], Bm, 1, 1, st));
-      HIP_OK(gpb::lap_deriv_mid(Bm, nul, Ds, nul, nul, n, 1, 1, 0, dir, nullptr, st));
-      HIP_OK(gpb::lap_Bt(lv, n, dir, S0, 1, 1, st));
-      HIP_OK(gpb::lap_mul(fwd_g, n, xs[q], gv, 1, 1, st));
-      HIP_OK(gpb::lap_deriv_mid(Bm, gv, Ds, dDs, W, n, 1, 1, 1, dir, mnew, st));
-      HIP_OK(gpb::lap_Bt(lv, n, dir, S1, 1, 1, st));
-      HIP_OK(gpb::lap_mul(bwd_g, n, mnew, t1, 1, 1, st));
-      HIP_OK(gpb::lap_lincomb(S1, S1, t1, 1.0, -1.0, n, st));
-    }
-    if (vif_grad_vec_sums(h, s, &vg, Q4, st)) return -1;
-  }
-  HIP_OK(hipMemcpyAsync(s->h_go, go, sizeof(double) * go_need, hipMemcpyDeviceToHost, st));
-  if (lap_check_solves(s, st)) return -1;
-  HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * 8, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  // ---- host: control variates with one optimal c per parameter (:16776-16790), explicit + implicit derivative (:6641-6664) ----
-  const double* g = s->h_go;
-  const double* gvh = g + (size_t)10 * tc;
-  const double sum_rdw_D = s->h_o[4], sum_rdw_dD_D2 = s->h_o[5], sum_dD_D = s->h_o[6];
-  for (int j = 0; j < 2; ++j) {
-    std::vector<double> z1(t), zP(t);
-    double m1 = 0., mP = 0.;
-    for (int c = 0; c < t; ++c) {
-      if (j == 0) { z1[c] = g[c]; zP[c] = g[tc + c]; }
-      else {
-        z1[c] = g[2 * tc + c] - g[4 * tc + c];
-        zP[c] = (g[3 * tc + c] - g[5 * tc + c]) + (g[7 * tc + c] - g[9 * tc + c]);
-      }
-      m1 += z1[c]; mP += zP[c];
-    }
-    m1 /= t; mP /= t;
-    if (vif) {                                 // CalcGradNegMargLikelihoodLaplaceApproxFSVA, covariance parameters (likelihoods.h:5413-5520)
-      const double mSm0 = (j == 0) ? gvh[0] : gvh[2] - gvh[4];
-      const double sSm0 = (j == 0) ? gvh[1] : gvh[3] - gvh[5];
-      double parts4[4];
-      grad2_host[j] = vif_grad_assemble(s, vg, j, t, tc, z1.data(), mSm0, sSm0, parts4);
-      if (parts_host) for (int q = 0; q < 4; ++q) parts_host[4 * j + q] = parts4[q];
-      continue;
-    }
-    if (pc) {                                  // d logdet / d theta_j = -mean_c (Sigma U_c)' SigmaI_deriv (Sigma P^-1 Z_c)  (:16734)
-      const double dlp = -1.0 * m1;
-      const double mSm = (j == 0) ? gvh[0] : gvh[2] - gvh[4];
-      const double sSm = (j == 0) ? gvh[1] : gvh[3] - gvh[5];
-      grad2_host[j] = 0.5 * (mSm + dlp) - sSm;
-      if (parts_host) { parts_host[4 * j] = mSm; parts_host[4 * j + 1] = dlp; parts_host[4 * j + 2] = 0.; parts_host[4 * j + 3] = -sSm; }
-      continue;
-    }
-    double dl = m1, trD;
-    if (j == 0) { dl += n; trD = -sum_rdw_D; }
-    else { dl += sum_dD_D; trD = -sum_rdw_dD_D2; }
-    double cov = 0., var = 0.;
-    for (int c = 0; c < t; ++c) { cov += (z1[c] - m1) * (zP[c] - mP); var += (zP[c] - mP) * (zP[c] - mP); }
-    cov /= t; var /= t;
-    const double copt = (var == 0.) ? 1. : cov / var;
-    dl += copt * trD - copt * mP;
-    const double mSm = (j == 0) ? gvh[0] : gvh[2] - gvh[4];
-    const double sSm = (j == 0) ? gvh[1] : gvh[3] - gvh[5];
-    grad2_host[j] = 0.5 * (mSm + dl) - sSm;
-    if (parts_host) { parts_host[4 * j] = mSm; parts_host[4 * j + 1] = dl; parts_host[4 * j + 2] = copt; parts_host[4 * j + 3] = -sSm; }
-  }
-  s->gvec_state = true;
-  if (vecs_host) {
-    std::vector<double> tmp((size_t)2 * n);
-    HIP_OK(hipMemcpyAsync(tmp.data(), dld, vb, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(tmp.data() + n, sv, vb, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) { vecs_host[i] = tmp[s->sigma[i]]; vecs_host[(size_t)n + i] = tmp[(size_t)n + s->sigma[i]]; }
-  }
   return 0;
 }
 // One block solve of the predictive variances: X += (Sigma^-1 + W)^-1 R for the right-hand sides in w.R by preconditioned CG ('vadu', the solver of the mode finding), the cnt
@@ -2726,13 +2444,6 @@ int gpb_hip_vecchia_laplace_eval(gpb_hip_vecchia_t* h, int cov_type, double var,
   API_END();
 }
 
-int gpb_hip_vecchia_laplace_grad_current(gpb_hip_vecchia_t* h, int cg_max_num_it, double cg_delta_conv, double* grad2_host,
-                                         double* parts8_host, double* vecs2n_host) {
-  API_BEGIN();
-  if (laplace_grad_current(h, cg_max_num_it, cg_delta_conv, grad2_host, parts8_host, vecs2n_host)) return -1;
-  API_END();
-}
-
 int gpb_hip_vecchia_laplace_reset_mode_to_previous(gpb_hip_vecchia_t* h) {
   API_BEGIN();
   if (!h || !h->lap || !h->lap->d_gvec || !h->lap->d_vec) return fail("no mode has been found yet");
@@ -2742,162 +2453,6 @@ int gpb_hip_vecchia_laplace_reset_mode_to_previous(gpb_hip_vecchia_t* h) {
   HIP_OK(hipStreamSynchronize(h->stream));
   s->grad_state = false; s->gvec_state = false;
   s->has_mode = true;          // a failed mode finding (NaN) is followed by this reset: the next one warm-starts from the restored mode
-  API_END();
-}
-
-// Boosting gradient for non-Gaussian data at the state of the last gpb_hip_vecchia_laplace_grad_current: d(-mll) / dF, Vecchia order
-// (CalcGradNegMargLikelihoodLaplaceApproxVecchia with calc_F_grad, likelihoods.h:6996-7001).
-int gpb_hip_vecchia_laplace_grad_F_current(gpb_hip_vecchia_t* h, double* gradF_host) {
-  API_BEGIN();
-  // (full-scale Vecchia handles too: CalcGradNegMargLikelihoodLaplaceApproxFSVA's calc_F_grad part, likelihoods.h:5598-5604, is the same expression in d logdet / d mode and the implicit solve)
-  if (!h || !gradF_host) return fail("null argument");
-  LaplaceState* s = h->lap;
-  if (!s || !s->grad_state || !s->gvec_state) return fail("the gradient wrt the fixed effects needs the state of gpb_hip_vecchia_laplace_grad_current");
-  HIP_OK(hipSetDevice(h->device));
-  const int n = h->n;
-  const LapWork w = lap_work(h, s, s->g_t);
-  if (!s->re_ptr.empty()) {
-    // repeated locations: per DATUM, in the order labels / fixed effects were handed over (grouped by random effect, Vecchia order of the random
-    // effects) -- the data-scale form of likelihoods.h:6944-6966
-    const int nd = s->n_data;
-    if (!s->d_dptr) return fail("the data map has not been uploaded (no evaluation since gpb_hip_vecchia_laplace_set_data_map)");
-    DevBuf<double> d_out;
-    HIP_OK(d_out.alloc((size_t)nd));
-    HIP_OK(gpb::lap_grad_F_map(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.dW3, w.sv, n, s->d_dptr, d_out, h->stream));
-    std::vector<double> tmp(nd);
-    HIP_OK(hipMemcpyAsync(tmp.data(), d_out, sizeof(double) * (size_t)nd, hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    std::vector<int> inv(n), sptr(n + 1);                     // storage slot -> Vecchia position; CSR of the data in storage order (as laplace_eval)
-    for (int i = 0; i < n; ++i) inv[s->sigma[i]] = i;
-    sptr[0] = 0;
-    for (int p = 0; p < n; ++p) sptr[p + 1] = sptr[p] + (s->re_ptr[inv[p] + 1] - s->re_ptr[inv[p]]);
-    for (int i = 0; i < n; ++i) {
-      const int p = s->sigma[i], cnt = s->re_ptr[i + 1] - s->re_ptr[i];
-      for (int k = 0; k < cnt; ++k) gradF_host[s->re_ptr[i] + k] = tmp[sptr[p] + k];
-    }
-    return 0;
-  }
-  HIP_OK(gpb::lap_grad_F(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.sv, n, w.t2, h->stream));      // (t2: free between evaluations)
-  std::vector<double> tmp(n);
-  HIP_OK(hipMemcpyAsync(tmp.data(), w.t2, w.vb, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < n; ++i) gradF_host[i] = tmp[s->sigma[i]];
-  API_END();
-}
-
-// Gradient of the negative approximate marginal log-likelihood wrt log(auxiliary parameter) at the state of the last gpb_hip_vecchia_laplace_grad_current
-// (CalcGradNegMargLikelihoodLaplaceApproxVecchia's calc_aux_par_grad branch, likelihoods.h:6743-6808): out4 = { gradient, CalcGradNegLogLikAuxPars
-// part, 0.5 * log-determinant part, implicit part }.
-int gpb_hip_vecchia_laplace_grad_aux_current(gpb_hip_vecchia_t* h, double* out4_host) {
-  API_BEGIN();
-  if (!h || !out4_host) return fail("null argument");
-  LaplaceState* s = h->lap;
-  if (!s || !gpb::lik_has_aux(s->link)) return fail("gpb_hip_vecchia_laplace_grad_aux_current: the likelihood has no auxiliary parameter");
-  if (!s->grad_state || !s->gvec_state) return fail("the gradient wrt the auxiliary parameter needs the state of gpb_hip_vecchia_laplace_grad_current");
-  HIP_OK(hipSetDevice(h->device));
-  const int n = h->n;
-  const int nd = s->re_ptr.empty() ? n : s->n_data;
-  const LapWork w = lap_work(h, s, s->g_t);
-  HIP_OK(gpb::lap_aux_grad(s->link, w.mode, s->resp(), s->has_fe ? s->d_fe : nullptr, w.dld, w.dW3, w.sv, n, s->d_dptr, s->d_o, h->stream));
-  double o3[3];
-  HIP_OK(hipMemcpyAsync(o3, s->d_o, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  const double r = s->aux;
-  if (!gpb::lik_info_depends_on_mode(s->link)) {
-    // gaussian_latent (one parameter, the error variance: CalcGradNegLogLikAuxPars :14262-14274 = 0.5 n - 0.5 / aux sum w resid^2, information 1 / aux,
-    // d information / d log aux = -1 / aux :14881-14890): exactly the structure of lognormal.
-    // lognormal (one parameter, the variance of log y: CalcGradNegLogLikAuxPars :14275-14286, information 1 / aux, d information / d log aux = -1 / aux :14891-14900): the
-    // structure of t below with ONE parameter.
-    // t with the Fisher-Laplace approximation (likelihoods.h:6800-6815, grad_information_wrt_mode_non_zero_ = false): per parameter (log scale, log df)
-    //   CalcGradNegLogLikAuxPars (:14241-14262) + 0.5 tr((Sigma^-1 + W)^-1 dW / d log aux), no implicit part; the trace by CalcLogDetStochDerivAuxParVecchia's vadu branch
-    //   (:16838-16856) from U and PI_Z of the log-determinant's block CG, dW_r / d log aux = (sum of the weights of r's data) dFI / d log aux (:15369-15400).  out: 4 doubles per parameter.
-    const int n_aux_fl = gpb::lik_num_aux(s->link);
-    const double nu = s->aux2, sigma2 = r * r;
-    // per parameter: CalcGradNegLogLikAuxPars from the kernel's sums; FI = the information per unit weight, dFI = d FI / d log(parameter)
-    double g_scale, FI = 1. / r, dFI[2] = { -1. / r, 0. };      // (lognormal, gaussian_latent: one parameter, FI = 1 / aux)
-    const double g_df = (o3[1] + nd * (-1.0 + nu * (host_digamma((nu + 1.) / 2.) - host_digamma(nu / 2.)))) / -2.0;
-    switch (s->link) {
-      case gpb::kT: g_scale = o3[0] + nd; FI = (nu + 1.) / (nu + 3.) / sigma2; dFI[0] = -2. * (nu + 1.) / (nu + 3.) / sigma2; dFI[1] = nu * 2. / sigma2 / (nu + 3.) / (nu + 3.); break;
-      case gpb::kLogNormal: g_scale = o3[0]; break;
-      case gpb::kGaussianLatent: g_scale = -0.5 / r * o3[0] + 0.5 * nd; break;
-      default: return fail("gpb_hip_vecchia_laplace_grad_aux_current: the Fisher-Laplace gradient of likelihood id %d is missing", s->link);
-    }
-    const int NCB = w.NCB, t = s->g_t, tch = w.tch, tc = w.tc;
-    const size_t nb = w.nb;
-    hipStream_t st = h->stream;
-    const double *W = w.W, *rdw = w.rdw;
-    double *R = w.R, *T = w.T, *Z = w.Z;              // free after the log-determinant / the covariance-parameter gradient
-    const double *U = s->d_gblk, *PIZ = s->d_gblk + nb;
-    const gpb::LapLevels lv = make_levels(h, s);
-    // W_r = (sum of weights) FI  ->  the per-row weight sums are W / FI: dW / d log aux = W .* (dFI / FI)
-    if (s->pc_type != 0) {
-      // pivoted_cholesky / fitc branches (:16800-16837) with dW = f W:  stochastic -f mean_c U_c' (W^-1 P^-1 Z_c) + n f;  control variate -f mean_c (W^-1 P^-1 Z_c)' W (W^-1 P^-1 Z_c)
-      // against f [sum_i sdiag_i W_i - n] (pivoted_cholesky) / f [sum_i sdiag_i wp_i^2 / W_i - sum_i wp_i / W_i] (fitc); PIZ holds the probes Z here
-      const bool fitc = s->pc_type == 2;
-      if (fitc) { if (pc_apply(s, n, W, PIZ, R, tch, NCB, 0, st)) return -1; HIP_OK(gpb::pc_rowscale(R, W, n, tch, NCB, 1, R, st)); }
-      else if (pc_apply(s, n, W, PIZ, R, tch, NCB, 1, st)) return -1;                                // R = W^-1 P^-1 Z
-      HIP_OK(gpb::pc_rowscale(R, W, n, tch, NCB, 0, Z, st));                                         // W .* R
-      if (s->go_cap < (size_t)4 * tc + 2) return fail("internal: the gradient's reduction buffer is missing (gpb_hip_vecchia_laplace_grad_current first)");
-      HIP_OK(gpb::lap_coldots(U, U, R, n, tch, NCB, s->d_go, st));                                   // U_c . R_c
-      HIP_OK(gpb::lap_coldots(R, R, Z, n, tch, NCB, s->d_go + (size_t)2 * tc, st));                  // R_c . (W R_c)
-      HIP_OK(gpb::pc_aux_sums(s->d_pcL, s->d_pcM, W, fitc ? s->d_pcwp : nullptr, n, s->pc_k, s->d_o, st));
-      HIP_OK(hipMemcpyAsync(s->h_go, s->d_go, sizeof(double) * ((size_t)4 * tc + 2), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      for (int ia = 0; ia < n_aux_fl; ++ia) {
-        const double f = dFI[ia] / FI;
-        double m1 = 0., mP = 0.;
-        for (int c = 0; c < t; ++c) { m1 += -f * s->h_go[c]; mP += -f * s->h_go[(size_t)2 * tc + c]; }
-        m1 /= t; mP /= t;
-        double cov = 0., var = 0.;
-        const double tr_WI_W = f * n;
-        const double det = fitc ? f * s->h_o[0] - f * s->h_o[1] : f * s->h_o[0] - tr_WI_W;
-        // (full-scale Vecchia, likelihoods.h:5666-5672: CalcOptimalC centres the control variate with its deterministic trace; the Vecchia path, :16830-16837, with the samples' mean)
-        const double bc = h->vif_k > 0 ? det : mP;
-        for (int c = 0; c < t; ++c) { const double a1 = -f * s->h_go[c] - m1, b1 = -f * s->h_go[(size_t)2 * tc + c] - bc; cov += a1 * b1; var += b1 * b1; }
-        cov /= t; var /= t;
-        const double copt = (var == 0.) ? 1. : cov / var;
-        const double ddet = m1 + tr_WI_W + copt * det - copt * mP;
-        const double nld = ia == 0 ? g_scale : g_df;
-        out4_host[4 * ia] = nld + 0.5 * ddet; out4_host[4 * ia + 1] = nld; out4_host[4 * ia + 2] = 0.5 * ddet; out4_host[4 * ia + 3] = 0.;
-      }
-      return 0;
-    }
-    HIP_OK(gpb::lap_B(lv, n, PIZ, R, tch, NCB, st));                 // B PI_Z
-    HIP_OK(gpb::pc_rowscale(PIZ, W, n, tch, NCB, 0, T, st));         // W .* PI_Z
-    HIP_OK(gpb::pc_rowscale(R, W, n, tch, NCB, 0, Z, st));           // W .* (B PI_Z)
-    const size_t go_need = (size_t)4 * tc + 2;
-    if (s->go_cap < go_need) return fail("internal: the gradient's reduction buffer is missing (gpb_hip_vecchia_laplace_grad_current first)");
-    HIP_OK(gpb::lap_coldots(U, U, T, n, tch, NCB, s->d_go, st));                    // U_c . (W PI_Z_c)
-    HIP_OK(gpb::lap_coldots(R, R, Z, n, tch, NCB, s->d_go + (size_t)2 * tc, st));   // (B PI_Z_c) . (W B PI_Z_c)
-    HIP_OK(gpb::lap_dot(rdw, W, n, s->d_o, st));                                    // sum rdw W
-    HIP_OK(hipMemcpyAsync(s->h_go, s->d_go, sizeof(double) * go_need, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(s->h_o, s->d_o, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (int ia = 0; ia < n_aux_fl; ++ia) {
-      const double f = dFI[ia] / FI;
-      double m1 = 0., mP = 0.;
-      for (int c = 0; c < t; ++c) { m1 += f * s->h_go[c]; mP += f * s->h_go[(size_t)2 * tc + c]; }
-      m1 /= t; mP /= t;
-      double cov = 0., var = 0.;
-      for (int c = 0; c < t; ++c) { const double a1 = f * s->h_go[c] - m1, b1 = f * s->h_go[(size_t)2 * tc + c] - mP; cov += a1 * b1; var += b1 * b1; }
-      cov /= t; var /= t;
-      const double copt = (var == 0.) ? 1. : cov / var;
-      const double ddet = m1 + copt * (f * s->h_o[0]) - copt * mP;
-      const double nld = ia == 0 ? g_scale : g_df;
-      out4_host[4 * ia] = nld + 0.5 * ddet; out4_host[4 * ia + 1] = nld; out4_host[4 * ia + 2] = 0.5 * ddet; out4_host[4 * ia + 3] = 0.;
-    }
-    return 0;
-  }
-  double nld;
-  switch (s->link) {      // CalcGradNegLogLikAuxPars
-    case gpb::kBeta: nld = -r * o3[0]; break;      // grad[0] = -precision * sum_d w_d (...) (likelihoods.h:14229-14241)
-    case gpb::kGamma: nld = o3[0] - nd * (std::log(r) + 1.0 - host_digamma(r)) - s->sum_log_y; nld *= r; break;      // :14189-14202
-    case gpb::kNegativeBinomial: nld = o3[0] + nd * r * (host_digamma(r) - std::log(r) - 1.0); break;      // :14203-14215
-    default: return fail("gpb_hip_vecchia_laplace_grad_aux_current: the gradient of likelihood id %d is missing", s->link);
-  }
-  out4_host[0] = nld + 0.5 * o3[1] + o3[2];
-  out4_host[1] = nld; out4_host[2] = 0.5 * o3[1]; out4_host[3] = o3[2];
   API_END();
 }
 
@@ -2912,124 +2467,6 @@ int gpb_hip_vecchia_laplace_get_aux_pars(gpb_hip_vecchia_t* h, double* aux_out, 
 
 // test seam: dA / d log(range) and dD / d log(range) of the factor without nugget at (var, a), Vecchia order (checked against
 // orc_vecchia_factor's A_grad / D_grad)
-/* Standard errors of (sigma2, sigma1_2, rho) of a Gaussian Vecchia model from the stochastic (Hutchinson) Fisher information on the ORIGINAL
-   scale: REModelTemplate::CalcFisherInformation_Vecchia (include/GPBoost/re_model_template.h:10137-10230, the default since
-   use_stochastic_trace_for_Fisher_information_Vecchia_ = true, :6033) behind CalcStdDevCovPar / GPB_GetCovPar(calc_std_dev = true):
-       v_0 = Psi^-1 z,   v_k = B' D^-1 (-dB_k Psi z + dD_k B^-T z) - dB_k' B^-T z,   FI_kl = mean_z (v_k . v_l) / 2,   se = sqrt(diag(FI^-1))
-   with the reference's probe vectors (GenRandVecNormalParallel(seed_rand_vec_trace, run id 0)).  Everything O(n t) runs on the device with the
-   level-scheduled solves of the Laplace path: ONE pass of the two triangular solves gives B^-T Z and B^-1 D B^-T Z for the whole probe
-   block; dB_k = -dA_k come from the per-point derivative kernel (nugget included) and are multiplied in the level-ordered layouts.
-   With f_0 = 1 / sigma2, f_var = 1 / sigma1_2, f_rho = -1 / rho (chain rule from the log scale of the transformed parameters):
-       v_0 = f_0 B' D^-1 B z,        v_k = f_k [ B' D^-1 (dA_k U + dD_k o T) + dA_k' T ],   T = B^-T z, U = B^-1 (D o T)   (sigma2 cancels). */
-int gpb_hip_vecchia_fisher_std_errors(gpb_hip_vecchia_t* h, int cov_type, double sigma2, double sigma1_2, double rho, double ratio, double a,
-                                      int num_rand_vec, int seed_rand_vec, double* se3_host) {
-  API_BEGIN();
-  if (!h || !se3_host) return fail("null argument");
-  if (!h->has_nn) return fail("neighbours have not been determined");
-  if (h->i_begin != 0 || h->i_end != h->n) return fail("the Fisher information needs the whole factor on one device (shard is [%d,%d))", h->i_begin, h->i_end);
-  if (num_rand_vec < 1) return fail("num_rand_vec must be positive");
-  if (h->m > 126) return fail("standard errors: the per-point derivative kernel handles at most 126 neighbours (this model has %d)", h->m);
-  if (h->d > 3) return fail("standard errors: the per-point derivative kernel handles coordinate dimensions 1..3 (this model has %d)", h->d);
-  HIP_OK(hipSetDevice(h->device));
-  if (!h->lap) h->lap = new LaplaceState();
-  LaplaceState* s = h->lap;
-  s->grad_state = false; s->gvec_state = false;
-  const int n = h->n, m = h->m;
-  hipStream_t st = h->stream;
-  if (alloc_factor(h)) return -1;
-  {
-    if (lap_launch_factor(h, cov_type, ratio, a, 1)) return -1;
-    HIP_OK(hipStreamSynchronize(st));
-    h->has_factor = false; h->u_stale = false; h->has_yaux = false;   // the factor on the device no longer belongs to a y_aux computed earlier
-  }
-  if (!h->has_transpose && build_transpose(h)) return -1;
-  if (!h->has_levels && build_levels(h, s)) return -1;
-  if (!s->d_Ds) HIP_OK(hipMalloc(&s->d_Ds, sizeof(double) * (size_t)n));
-  HIP_OK(gpb::lap_scatter(h->d_D, s->d_sigma, n, s->d_Ds, st));
-  const int t = num_rand_vec;
-  const LapWork w = lap_work(h, s, t);                  // (the chunk geometry; this computation has its own workspace)
-  const int NCB = w.NCB, tch = w.tch, tc = w.tc;
-  const size_t blk = w.nb;
-  // workspace of this computation only (freed at the end): probes + 8 blocks + two derivative sets
-  DevBuf<double> d_ws;
-  HIP_OK(d_ws.alloc(blk * 9 + (size_t)n * 2));
-  HIP_OK(hipMemsetAsync(d_ws, 0, sizeof(double) * (blk * 9 + (size_t)n * 2), st));
-  double *Z = d_ws, *T = d_ws + blk, *U = d_ws + 2 * blk, *V0 = d_ws + 3 * blk, *V1 = d_ws + 4 * blk, *V2 = d_ws + 5 * blk, *P = d_ws + 6 * blk,
-         *H = d_ws + 7 * blk, *Q = d_ws + 8 * blk, *dDs = d_ws + 9 * blk, *tmpn = d_ws + 9 * blk + n;
-  {
-    std::vector<double> rv(blk), colbuf(n);
-    for (int c = 0; c < t; ++c) {           // column c from mt19937(seed_seq{seed, run_id lo, run_id hi, c}), run_id = 0
-      std::normal_distribution<double> ndist(0.0, 1.0);
-      std::seed_seq seq{ static_cast<uint32_t>(seed_rand_vec), 0u, 0u, static_cast<uint32_t>(c) };
-      std::mt19937 gen(seq);
-      for (int i = 0; i < n; ++i) colbuf[i] = ndist(gen);
-      double* dst = rv.data() + (size_t)(c / NCB) * n * NCB + (c % NCB);
-      for (int i = 0; i < n; ++i) dst[(size_t)s->sigma[i] * NCB] = colbuf[i];
-    }                                        // the columns padding the last chunk stay zero: they contribute nothing and are not averaged
-    HIP_OK(hipMemcpyAsync(Z, rv.data(), sizeof(double) * blk, hipMemcpyHostToDevice, st));
-    HIP_OK(hipStreamSynchronize(st));
-  }
-  const gpb::LapLevels lv = make_levels(h, s);
-  for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd })
-    HIP_OK(gpb::lap_permute_factor(h->d_A, tr->hpos, tr->opos, (size_t)tr->nslots * 32, tr->novf, tr->hent, tr->oent, st));
-  HIP_OK(gpb::lap_dense_build(lv.fdense, h->d_A, st));      // the inverses of the solves' dense blocks for this A
-  HIP_OK(gpb::lap_dense_build(lv.bdense, h->d_A, st));
-  const double* Ds = s->d_Ds;
-  HIP_OK(gpb::lap_vadu(lv, n, Ds, Z, U, T, tch, NCB, st));                       // T = B^-T Z,  U = B^-1 (D o T)
-  HIP_OK(gpb::lap_apply(lv, n, Ds, nullptr, Z, V0, P, tch, NCB, st));             // V0 = B' D^-1 B Z
-  if (!s->d_dA) {
-    HIP_OK(hipMalloc(&s->d_dA, sizeof(double) * (size_t)n * m));
-    HIP_OK(hipMalloc(&s->d_dD, sizeof(double) * (size_t)n));
-  }
-  for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd }) {
-    const size_t nh = (size_t)tr->nslots * 32, no = tr->novf > 0 ? tr->novf : 1;
-    if (!tr->hent_g) {
-      HIP_OK(hipMalloc(&tr->hent_g, sizeof(gpb::LapEnt) * nh));
-      HIP_OK(hipMalloc(&tr->oent_g, sizeof(gpb::LapEnt) * no));
-      HIP_OK(hipMemcpyAsync(tr->hent_g, tr->hent, sizeof(gpb::LapEnt) * nh, hipMemcpyDeviceToDevice, st));
-      HIP_OK(hipMemcpyAsync(tr->oent_g, tr->oent, sizeof(gpb::LapEnt) * no, hipMemcpyDeviceToDevice, st));
-    }
-  }
-  gpb::LapTri fwd_g = lv.fwd, bwd_g = lv.bwd;
-  fwd_g.hent = s->fwd.hent_g; fwd_g.oent = s->fwd.oent_g;
-  bwd_g.hent = s->bwd.hent_g; bwd_g.oent = s->bwd.oent_g;
-  (void)tmpn;
-  for (int k = 0; k < 2; ++k) {            // k = 0: variance ratio, k = 1: range  (derivatives wrt the LOG of the transformed parameters)
-    double* Vk = k == 0 ? V1 : V2;
-    HIP_OK(gpb::lap_factor_deriv(h->d_pts, h->d_nn, h->d_A, n, m, cov_type, h->d == 3 ? 1 : 0, ratio, a, ratio + 1.0, 1.0, k == 0 ? 1 : 0,
-                                 s->d_dA, s->d_dD, st));
-    HIP_OK(gpb::lap_scatter(s->d_dD, s->d_sigma, n, dDs, st));
-    for (LaplaceState::Tri* tr : { &s->fwd, &s->bwd })
-      HIP_OK(gpb::lap_permute_factor(s->d_dA, tr->hpos, tr->opos, (size_t)tr->nslots * 32, tr->novf, tr->hent_g, tr->oent_g, st));
-    HIP_OK(gpb::lap_mul(fwd_g, n, U, P, tch, NCB, st));                            // P = dA_k U
-    HIP_OK(gpb::lap_fisher_mid(P, T, Ds, dDs, n, tch, NCB, H, st));                 // H = (dA_k U + dD_k o T) / D
-    HIP_OK(gpb::lap_Bt(lv, n, H, Q, tch, NCB, st));                                 // Q = B' H
-    HIP_OK(gpb::lap_mul(bwd_g, n, T, P, tch, NCB, st));                             // P = dA_k' T
-    HIP_OK(gpb::lap_lincomb(Vk, Q, P, 1.0, 1.0, (int)blk, st));                     // V_k = Q + P
-  }
-  DevBuf<double> d_dots;
-  HIP_OK(d_dots.alloc((size_t)6 * tc));
-  HIP_OK(gpb::lap_coldots(V0, V1, V0, n, tch, NCB, d_dots, st));                    // 00, 10
-  HIP_OK(gpb::lap_coldots(V1, V2, V1, n, tch, NCB, d_dots + 2 * tc, st));           // 11, 21
-  HIP_OK(gpb::lap_coldots(V0, V2, V2, n, tch, NCB, d_dots + 4 * tc, st));           // 02, 22
-  std::vector<double> dots((size_t)6 * tc);
-  HIP_OK(hipMemcpyAsync(dots.data(), d_dots, sizeof(double) * dots.size(), hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  h->has_levels = h->has_levels;            // (level schedules stay valid: they depend on the neighbour table only)
-  auto meanc = [&](int block) { double acc = 0.; for (int c = 0; c < t; ++c) acc += dots[(size_t)block * tc + c]; return acc / t; };
-  const double f[3] = { 1.0 / sigma2, 1.0 / sigma1_2, -1.0 / rho };
-  double FI[3][3];
-  FI[0][0] = meanc(0) * f[0] * f[0] / 2.; FI[1][0] = FI[0][1] = meanc(1) * f[1] * f[0] / 2.;
-  FI[1][1] = meanc(2) * f[1] * f[1] / 2.; FI[2][1] = FI[1][2] = meanc(3) * f[2] * f[1] / 2.;
-  FI[2][0] = FI[0][2] = meanc(4) * f[0] * f[2] / 2.; FI[2][2] = meanc(5) * f[2] * f[2] / 2.;
-  // diagonal of the inverse of the symmetric 3 x 3 matrix by cofactors
-  const double c00 = FI[1][1] * FI[2][2] - FI[1][2] * FI[2][1], c11 = FI[0][0] * FI[2][2] - FI[0][2] * FI[2][0], c22 = FI[0][0] * FI[1][1] - FI[0][1] * FI[1][0];
-  const double det = FI[0][0] * c00 - FI[0][1] * (FI[1][0] * FI[2][2] - FI[1][2] * FI[2][0]) + FI[0][2] * (FI[1][0] * FI[2][1] - FI[1][1] * FI[2][0]);
-  if (!(det > 0.)) return fail("the Fisher information is not positive definite (det = %g)", det);
-  se3_host[0] = std::sqrt(c00 / det); se3_host[1] = std::sqrt(c11 / det); se3_host[2] = std::sqrt(c22 / det);
-  API_END();
-}
-
 int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int cov_type, double var, double a, double* dA_host, double* dD_host) {
   API_BEGIN();
   if (!h || !dA_host || !dD_host) return fail("null argument");
@@ -3054,3 +2491,6 @@ int gpb_hip_vecchia_laplace_range_deriv(gpb_hip_vecchia_t* h, int cov_type, doub
 }
 
 }  // extern "C"
+
+// The gradient half: gpb_hip_vecchia_laplace_grad_current in stages, the gradients wrt F and the auxiliary parameters, the standard errors of a Gaussian Vecchia model.
+#include "gpb_laplace_grad.inc"

@@ -185,4 +185,20 @@ inline void ip_cov(const double* ip, int k, int d, IpLayout layout, MaternForm f
     }
 }
 
+// ---- 10. optimal coefficient of a control variate (CalcOptimalC, CG_utils.cpp:1053-1090 of the reference): c = cov(z1, zP) / var(zP) over t samples, 1 where the
+// variance is 0.  The control variates are centred with *centre (their deterministic expectation) or, centre = null, with their sample mean; z1 always with its
+// mean.  Order: both means as running sums over c ascending, then divided by t; cov and var as running sums of the centred products over c ascending, then divided by t.
+// The caller scales its samples first; the estimate it forms is mean1 - c (meanP - expectation).
+struct OptimalC { double c, mean1, meanP; };
+inline OptimalC optimal_c(const double* z1, const double* zP, int t, const double* centre) {
+  double m1 = 0., mP = 0.;
+  for (int c = 0; c < t; ++c) { m1 += z1[c]; mP += zP[c]; }
+  m1 /= t; mP /= t;
+  const double cP = centre ? *centre : mP;
+  double cov = 0., var = 0.;
+  for (int c = 0; c < t; ++c) { const double a1 = z1[c] - m1, b1 = zP[c] - cP; cov += a1 * b1; var += b1 * b1; }
+  cov /= t; var /= t;
+  return OptimalC{ (var == 0.) ? 1. : cov / var, m1, mP };
+}
+
 }  // namespace gpb_sm

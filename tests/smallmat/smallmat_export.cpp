@@ -23,6 +23,11 @@ SM_EXPORT double sm_matern(int which, int cov_type, double scale, double r) {
   return which == 0 ? sm::matern_gaussian_paths(cov_type, scale, r) : which == 1 ? sm::matern_gaussian_paths_dloga(cov_type, scale, r)
        : which == 2 ? sm::matern_laplace_paths(cov_type, scale, r) : sm::matern_laplace_paths_dloga(cov_type, scale, r);
 }
+// centred_at_value: the control variates are centred with *centre, otherwise with their sample mean; out3 = { c, mean of z1, mean of zP }
+SM_EXPORT void sm_optimal_c(const double* z1, const double* zP, int t, int centred_at_value, double centre, double* out3) {
+  const sm::OptimalC oc = sm::optimal_c(z1, zP, t, centred_at_value ? &centre : nullptr);
+  out3[0] = oc.c; out3[1] = oc.mean1; out3[2] = oc.meanP;
+}
 SM_EXPORT void sm_ip_cov(const double* ip, int k, int d, int row_major_kx3, int laplace_form, int cov_type, double var, double a, double* Sm, double* dSm) {
   sm::ip_cov(ip, k, d, row_major_kx3 ? sm::IpLayout::RowMajorKx3 : sm::IpLayout::ColMajorKxD, laplace_form ? sm::MaternForm::LaplacePaths : sm::MaternForm::GaussianPaths,
              cov_type, var, a, Sm, dSm);

@@ -45,6 +45,8 @@ static int run(int k) {
   sm::matmul(inv.data(), inv2.data(), k, P.data());
   for (auto& v : packed) v = rnd();
   sm::sym_from_packed(packed.data(), k, sym.data());
+  const sm::OptimalC oc = sm::optimal_c(x.data(), dg.data(), k, nullptr), oc2 = sm::optimal_c(x.data(), dg.data(), k, &sl);      // t = k samples, exactly sized
+  errs += check(std::isfinite(oc.c) && std::isfinite(oc2.c) && oc.mean1 == oc2.mean1 && (k > 1 || oc.c == 1.), "optimal_c", k);
   for (int c = 0; c < k; ++c) errs += check(std::isfinite(dg[c]) && dg[c] > 0. && std::fabs(dg[c] - inv[(size_t)c * k + c]) <= 1e-12 * dg[c], "inverse_diagonal against spd_inverse_from_tri", k);
   for (int d = 1; d <= 3; ++d) {
     std::vector<double> cm((size_t)k * d), rm((size_t)k * 3, 0.), Sm((size_t)k * k), dSm((size_t)k * k), Sm2((size_t)k * k);

@@ -1,8 +1,13 @@
 """Pure-Python restatement of gpboost_amd/csrc/gpb_smallmat.h: float64 scalars (Python floats), one operation per step in the order the routine documents,
 math.exp / math.sqrt / math.log (the same libm as the library's).  Written from the call sites the header replaced, not from the header: the Cholesky here runs
 column by column as the Laplace sites did (the header runs row by row as the C API did), the triangular inverse is the C API's form.  Matrices are lists of rows.
-tests/test_smallmat.py asks the header for the same bits."""
+tests/test_smallmat.py asks the header for the same bits.
+
+optimal_c is the exception: a numpy restatement in extended precision, held to a rounding bound and not to bits (its four former copies are gone with the change
+that added it; tests/test_zz_laplace_grad_sites_gpu.py holds the sites to the bits they gave)."""
 import math
+
+import numpy as np
 
 
 def cholesky_lower(A, k):
@@ -163,3 +168,13 @@ def ip_cov(points, gaussian_form, cov_type, var, a):
             Sm[i][j] = Sm[j][i] = f(cov_type, var, r)
             dSm[i][j] = dSm[j][i] = g(cov_type, var, r)
     return Sm, dSm
+
+
+def optimal_c(z1, zP, centre=None):
+    """CalcOptimalC: c = cov(z1, zP) / var(zP) over the t samples, 1 where the variance is 0; zP centred with `centre` or, None, with its sample mean.
+    -> (c, mean1, meanP, the centred products a1 b1, the squares b1^2) in long double"""
+    z1, zP = np.asarray(z1, dtype=np.longdouble), np.asarray(zP, dtype=np.longdouble)
+    m1, mP = z1.mean(), zP.mean()
+    a1, b1 = z1 - m1, zP - (mP if centre is None else np.longdouble(centre))
+    cov, var = (a1 * b1).mean(), (b1 * b1).mean()
+    return (np.longdouble(1.0) if var == 0 else cov / var), m1, mP, a1 * b1, b1 * b1

@@ -186,3 +186,39 @@ def test_inducing_point_covariance(lib, k, d):
                 lib.sm_ip_cov(_p(ip), k, d, rm, lap, cov_type, C.c_double(var), C.c_double(a), _p(S2), None)      # the derivative is optional
                 assert np.array_equal(Sm, np.array(Sr)) and np.array_equal(dSm, np.array(dSr)) and np.array_equal(S2, Sm), (cov_type, lap, rm)
                 assert np.all(np.diag(Sm) == var)                                                                # no jitter: the caller's
+
+
+def _optimal_c(lib, z1, zP, centre=None):
+    out = np.full(3, PAD)
+    z1, zP = np.ascontiguousarray(z1, dtype=np.float64), np.ascontiguousarray(zP, dtype=np.float64)
+    lib.sm_optimal_c(_p(z1), _p(zP), len(z1), 0 if centre is None else 1, C.c_double(0.0 if centre is None else centre), _p(out))
+    return out
+
+
+@pytest.mark.parametrize("t", [1, 2, 10, 50])
+@pytest.mark.parametrize("centred", ["mean", "value"])
+def test_optimal_c(lib, t, centred):
+    """Samples of scale 1 around a mean of scale 1, so that centring loses nothing the bound does not cover.  A running sum of t terms divided by t is off by at most
+    t eps max|term|; c = cov / var inherits (d cov + |c| d var) / var, and `few` = 4 covers the roundings of the centred terms themselves."""
+    rng = np.random.default_rng(7 * t + (centred == "value"))
+    zP = 0.5 + rng.standard_normal(t)
+    z1 = 0.8 * zP + 0.3 * rng.standard_normal(t) - 0.2
+    centre = None if centred == "mean" else 0.5
+    c, m1, mP = _optimal_c(lib, z1, zP, centre)
+    cr, m1r, mPr, ab, bb = R.optimal_c(z1, zP, centre)
+    eps, few = np.finfo(np.float64).eps, 4
+    assert abs(m1 - m1r) <= t * eps * np.abs(z1).max() and abs(mP - mPr) <= t * eps * np.abs(zP).max()
+    if bb.mean() == 0:      # t = 1 centred with the mean
+        assert t == 1 and centre is None and c == 1.0
+    else:
+        tol = few * t * eps * (np.abs(ab).max() + abs(cr) * bb.max()) / bb.mean()
+        print("t = %d, %s: c = %.17g, off by %.3e, bound %.3e" % (t, centred, c, abs(c - cr), tol))
+        assert abs(c - cr) <= tol
+
+
+@pytest.mark.parametrize("centre", [None, 0.75])
+def test_optimal_c_is_one_without_variance(lib, centre):
+    """all control variates equal (0.75 t and its tenth are exact in float64): var == 0 -> c = 1, whatever the samples"""
+    z1 = np.random.default_rng(3).standard_normal(10)
+    c, m1, mP = _optimal_c(lib, z1, np.full(10, 0.75), centre)
+    assert c == 1.0 and mP == 0.75 and abs(m1 - z1.mean()) <= 10 * np.finfo(np.float64).eps * np.abs(z1).max()
