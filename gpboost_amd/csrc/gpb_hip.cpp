@@ -33,6 +33,7 @@
 #include "leaf_kernels.h"
 #include "nn_kernels.h"
 #include "tree_predict_kernels.h"
+#include "tree_shap_kernels.h"
 #include "vecchia_kernels.h"
 #include "vif_kernels.h"
 #include <fcntl.h>
@@ -466,13 +467,18 @@ struct gpb_hip_hist {
   // tree scoring (gpb_tree.inc, second half): the arrays of the last tree grown (what gpb_hip_hist_grow_tree handed to its caller), the stored trees
   // (tree_predict_kernels.h) on the host and on the device, an attached second matrix, and the staging of row lists and results
   struct LastTree { bool valid = false; int num_leaves = 0; std::vector<int> split_feature, default_left, left_child, right_child; std::vector<uint32_t> threshold;
-                    std::vector<double> leaf_value; } last_tree;
+                    std::vector<double> leaf_value; std::vector<int> leaf_count; } last_tree;
   std::vector<uint32_t> forest_words; std::vector<int> forest_desc;              // desc: 4 ints per tree {first word, num_leaves, stored bytes, 0}
   uint32_t* d_forest = nullptr; size_t forest_cap_words = 0; int* d_forest_desc = nullptr; int forest_cap_trees = 0;
   uint8_t* d_pred_rm = nullptr; int n_pred = 0;                                  // gpb_hip_hist_set_pred_bins: [n_pred][fpad]
   int* d_prows = nullptr; int* h_prows = nullptr; int prows_cap = 0;             // row list (+ multiplicities behind it): pinned host staging and device copy
   hipEvent_t ev_prows = nullptr; bool prows_pending = false;                     // the staging buffer's last copy (awaited before it is overwritten)
   double* d_pscore = nullptr; int pscore_cap = 0; int* d_pleaf = nullptr; int pleaf_cap = 0;
+  // per-feature contributions (gpb_tree.inc, last part; tree_shap_kernels.h): the path tables of the stored trees that have leaf counts, in the order the counts
+  // arrived; desc: 4 ints per tree {first word, num_leaves, largest number of elements of a leaf, 1 = has a table}; the tree's expected value per tree
+  std::vector<uint32_t> shap_words; std::vector<int> shap_desc; std::vector<double> shap_expected;
+  uint32_t* d_shap = nullptr; size_t shap_cap_words = 0; int* d_shap_desc = nullptr; int shap_cap_trees = 0; double* d_shap_ratio = nullptr;
+  double* d_pcontrib = nullptr; size_t pcontrib_cap = 0;
 };
 
 // column-major n x d coordinates -> the kernels' records {x0, x1, x2, 0} (the coordinates beyond the third travel in d_coords_nd)
@@ -2123,6 +2129,7 @@ int gpb_hip_hist_free(gpb_hip_hist_t* h) {
   if (h->h_cat_bits2) (void)hipHostFree(h->h_cat_bits2);
   h->comm.release(); dev_free(h->d_limbs);
   dev_free(h->d_forest); dev_free(h->d_forest_desc); dev_free(h->d_pred_rm); dev_free(h->d_prows); dev_free(h->d_pscore); dev_free(h->d_pleaf);
+  dev_free(h->d_shap); dev_free(h->d_shap_desc); dev_free(h->d_shap_ratio); dev_free(h->d_pcontrib);
   if (h->h_prows) (void)hipHostFree(h->h_prows);
   if (h->ev_prows) (void)hipEventDestroy(h->ev_prows);
   delete h;

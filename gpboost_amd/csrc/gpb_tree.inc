@@ -316,6 +316,7 @@ extern "C" int gpb_hip_hist_grow_tree(gpb_hip_hist_t* h, int32_t num_leaves, dou
     lt.split_feature.assign(split_feature_inner, split_feature_inner + nnodes); lt.threshold.assign(threshold_in_bin, threshold_in_bin + nnodes);
     lt.default_left.assign(default_left, default_left + nnodes); lt.left_child.assign(left_child, left_child + nnodes);
     lt.right_child.assign(right_child, right_child + nnodes); lt.leaf_value.assign(lval.begin(), lval.begin() + nleaves);
+    lt.leaf_count.assign(gcnt.begin(), gcnt.begin() + nleaves);
   }
   if (data_leaf_index) {
     if (nleaves == 1) {                              // never split: every row of the root is in leaf 0, rows outside a bag in none (-1)
@@ -582,6 +583,212 @@ int tree_predict_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_be
   return 0;
 }
 
+// ---- per-feature contributions (TreeSHAP) of stored trees (tree_shap_kernels.hip) ------------------------------------------------------------------------
+// Stands in for Tree::PredictContrib -> Tree::TreeSHAP (src/LightGBM/io/tree.cpp:827-998) on binned rows.  The recursion's unique path is compiled per leaf,
+// once, when the cover counts of a tree arrive (tree_shap_kernels.h); the kernel then works one (row, leaf) at a time.
+
+struct ShapElem { int col; uint32_t set[8]; double zero; };
+
+// The path table of one tree: per leaf the DISTINCT columns on its root-to-leaf path in order of first appearance, each with the AND of the go-left sets of its
+// nodes on the path (complemented for right turns) and the product of count(child) / count(node) over those nodes, multiplied root to leaf.  count(node) =
+// the sum of the leaf counts below it (the reference's internal_count_ after training).  Host only; the input is validated (a walk cannot spin or leave it).
+int tree_shap_paths(const char* who, int num_leaves, const int32_t* split_feature_inner, const int32_t* left_child, const int32_t* right_child,
+                    const uint32_t* node_sets8, const int32_t* leaf_count, std::vector<int>* first, std::vector<ShapElem>* elems) {
+  first->assign(1, 0); elems->clear();
+  if (num_leaves < 1) return fail("%s: invalid tree: num_leaves = %d", who, num_leaves);
+  if (num_leaves == 1) { first->push_back(0); return 0; }                      // no nodes, no elements, no counts needed
+  if (!split_feature_inner || !left_child || !right_child || !node_sets8 || !leaf_count) return fail("%s: null argument", who);
+  const int nn = num_leaves - 1;
+  for (int k = 0; k < num_leaves; ++k)
+    if (leaf_count[k] < 1) return fail("%s: leaf %d has the count %d (a leaf count is at least 1)", who, k, leaf_count[k]);
+  std::vector<long long> ncnt((size_t)nn, 0);
+  for (int i = nn - 1; i >= 0; --i) {
+    if (split_feature_inner[i] < 0) return fail("%s: invalid tree: node %d splits column %d", who, i, split_feature_inner[i]);
+    for (const int c : {left_child[i], right_child[i]}) {
+      if (c < 0) { if (~c >= num_leaves) return fail("%s: invalid tree: node %d points to leaf %d of %d", who, i, ~c, num_leaves); ncnt[(size_t)i] += leaf_count[~c]; }
+      else { if (c <= i || c >= nn) return fail("%s: invalid tree: node %d has the child node %d (children are later nodes, below %d)", who, i, c, nn); ncnt[(size_t)i] += ncnt[(size_t)c]; }
+    }
+  }
+  std::vector<std::vector<ShapElem>> paths((size_t)num_leaves);
+  std::vector<char> seen((size_t)num_leaves, 0);
+  std::vector<ShapElem> path;
+  int bad_leaf = -1;
+  std::function<void(int)> walk = [&](int node) {
+    const int f = split_feature_inner[node];
+    for (int side = 0; side < 2; ++side) {
+      const int c = side == 0 ? left_child[node] : right_child[node];
+      const double q = (double)(c < 0 ? (long long)leaf_count[~c] : ncnt[(size_t)c]) / (double)ncnt[(size_t)node];
+      size_t at = 0;
+      while (at < path.size() && path[at].col != f) ++at;
+      const bool fresh = at == path.size();
+      if (fresh) { ShapElem e; e.col = f; for (int w = 0; w < 8; ++w) e.set[w] = 0xffffffffu; e.zero = 1.0; path.push_back(e); }
+      const ShapElem saved = path[at];
+      for (int w = 0; w < 8; ++w) path[at].set[w] &= side == 0 ? node_sets8[8 * (size_t)node + w] : ~node_sets8[8 * (size_t)node + w];
+      path[at].zero *= q;
+      if (c < 0) { if (seen[(size_t)~c]) bad_leaf = ~c; else { seen[(size_t)~c] = 1; paths[(size_t)~c] = path; } }
+      else walk(c);
+      if (fresh) path.pop_back(); else path[at] = saved;
+    }
+  };
+  walk(0);
+  if (bad_leaf >= 0) return fail("%s: invalid tree: leaf %d is referenced more than once", who, bad_leaf);
+  for (int k = 0; k < num_leaves; ++k) {
+    if (!seen[(size_t)k]) return fail("%s: invalid tree: leaf %d is referenced 0 times", who, k);
+    if ((int)paths[(size_t)k].size() > GPB_SHAP_MAX_UNIQUE)
+      return fail("%s: the path to leaf %d has %d distinct columns, more than the %d the permutation weights stay accurate for", who, k, (int)paths[(size_t)k].size(),
+                  GPB_SHAP_MAX_UNIQUE);
+    elems->insert(elems->end(), paths[(size_t)k].begin(), paths[(size_t)k].end());
+    first->push_back((int)elems->size());
+  }
+  return 0;
+}
+
+// compile the path table of the stored tree tree_id from its cover counts (nullptr: a tree of one leaf), append it and bring the device copy up to date
+int shap_set_counts(gpb_hip_hist_t* h, const char* who, int tree_id, const int32_t* leaf_count) {
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  if (tree_id < 0 || tree_id >= ntrees) return fail("%s: tree %d: the forest holds %d (unknown tree id)", who, tree_id, ntrees);
+  const int nl = h->forest_desc[4 * (size_t)tree_id + 1], nn = nl - 1;
+  if (nl > 1 && !leaf_count) return fail("%s: null argument", who);
+  const uint32_t* w = h->forest_words.data() + (size_t)h->forest_desc[4 * (size_t)tree_id];
+  std::vector<int32_t> sf((size_t)nn), lc((size_t)nn), rc((size_t)nn);
+  std::vector<uint32_t> sets(8 * (size_t)nn);
+  for (int i = 0; i < nn; ++i) {
+    const uint32_t* nd = w + (size_t)i * GPB_TP_NODE_WORDS;
+    std::copy(nd, nd + 8, sets.begin() + 8 * (size_t)i);
+    sf[(size_t)i] = (int32_t)nd[8]; lc[(size_t)i] = (int32_t)nd[9]; rc[(size_t)i] = (int32_t)nd[10];
+  }
+  std::vector<int> first; std::vector<ShapElem> elems;
+  if (tree_shap_paths(who, nl, sf.data(), lc.data(), rc.data(), sets.data(), leaf_count, &first, &elems)) return -1;
+  std::vector<double> vals((size_t)nl);
+  std::memcpy(vals.data(), w + (size_t)nn * GPB_TP_NODE_WORDS, sizeof(double) * (size_t)nl);
+  double ev = vals[0];                                                         // Tree::ExpectedValue (tree.cpp:990-998)
+  if (nl > 1) {
+    double total = 0.0;
+    for (int k = 0; k < nl; ++k) total += (double)leaf_count[k];
+    ev = 0.0;
+    for (int k = 0; k < nl; ++k) ev += ((double)leaf_count[k] / total) * vals[(size_t)k];
+  }
+  const size_t w0 = h->shap_words.size(), nw = (gpb::tree_shap_table_words(nl, (int)elems.size()) + 3) / 4 * 4;
+  if (w0 + nw > (size_t)0x7fffffff) return fail("%s: the path tables are full", who);
+  int emax = 0;
+  for (int k = 0; k < nl; ++k) emax = std::max(emax, first[(size_t)k + 1] - first[(size_t)k]);
+  h->shap_words.resize(w0 + nw, 0u);
+  uint32_t* tb = h->shap_words.data() + w0;
+  std::memcpy(tb, &ev, sizeof(double));
+  std::memcpy(tb + 4, vals.data(), sizeof(double) * (size_t)nl);
+  std::memcpy(tb + 4 + 2 * (size_t)nl, first.data(), sizeof(int) * ((size_t)nl + 1));
+  uint32_t* eb = tb + 4 + 2 * (size_t)nl + gpb::tree_shap_first_words(nl);
+  for (size_t e = 0; e < elems.size(); ++e) {
+    uint32_t* x = eb + e * GPB_SHAP_ELEM_WORDS;
+    std::copy(elems[e].set, elems[e].set + 8, x);
+    x[8] = (uint32_t)elems[e].col;
+    const double z = elems[e].zero, invz = 1.0 / z;
+    std::memcpy(x + 12, &z, sizeof(double)); std::memcpy(x + 14, &invz, sizeof(double));
+  }
+  h->shap_desc.resize(4 * (size_t)ntrees, 0); h->shap_expected.resize((size_t)ntrees, 0.0);
+  const int desc[4] = {(int)w0, nl, emax, 1};
+  std::copy(desc, desc + 4, h->shap_desc.begin() + 4 * (size_t)tree_id);
+  h->shap_expected[(size_t)tree_id] = ev;
+  // device copy: no contribution kernel is reading the buffers; they grow by doubling; the new table and the (small) descriptor array are uploaded
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (!h->d_shap_ratio) {
+    std::vector<double> r(2 * (size_t)GPB_SHAP_RATIO_ENTRIES, 0.0);
+    for (int d = 0; d <= GPB_SHAP_MAX_UNIQUE; ++d)
+      for (int k = 0; k <= d + 1; ++k) {
+        r[(size_t)d * GPB_SHAP_RATIO_STRIDE + k] = (double)k / (double)(d + 1);
+        if (k > 0) r[(size_t)GPB_SHAP_RATIO_ENTRIES + (size_t)d * GPB_SHAP_RATIO_STRIDE + k] = (double)(d + 1) / (double)k;
+      }
+    HIP_OK(hipMalloc(&h->d_shap_ratio, sizeof(double) * r.size()));
+    HIP_OK(hipMemcpy(h->d_shap_ratio, r.data(), sizeof(double) * r.size(), hipMemcpyHostToDevice));
+  }
+  size_t from = w0;
+  if (h->shap_words.size() > h->shap_cap_words) {
+    const size_t cw = std::max<size_t>(2 * h->shap_words.size(), 1u << 14);
+    dev_free(h->d_shap); h->shap_cap_words = 0;
+    HIP_OK(hipMalloc(&h->d_shap, sizeof(uint32_t) * cw));
+    h->shap_cap_words = cw; from = 0;
+  }
+  if (ntrees > h->shap_cap_trees) {
+    const int ct = std::max(2 * ntrees, 64);
+    dev_free(h->d_shap_desc); h->shap_cap_trees = 0;
+    HIP_OK(hipMalloc(&h->d_shap_desc, sizeof(int) * 4 * (size_t)ct));
+    h->shap_cap_trees = ct;
+  }
+  HIP_OK(hipMemcpy(h->d_shap + from, h->shap_words.data() + from, sizeof(uint32_t) * (h->shap_words.size() - from), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->d_shap_desc, h->shap_desc.data(), sizeof(int) * h->shap_desc.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+bool shap_has_table(const gpb_hip_hist_t* h, int t) { return 4 * (size_t)t + 3 < h->shap_desc.size() && h->shap_desc[4 * (size_t)t + 3] == 1; }
+
+// One contribution call.  rows: HOST indices into the matrix `which` (nullptr: all its rows), no row twice.  d_out: device, [rows of the matrix][F + 1].
+int tree_shap_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_begin, int tree_end, const int32_t* rows, int cnt, double* d_out, int reps = 0,
+                   double* ms_avg = nullptr) {
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  if (tree_begin < 0 || tree_end > ntrees || tree_begin >= tree_end)
+    return fail("%s: trees [%d, %d): the forest holds %d (unknown tree id or empty range)", who, tree_begin, tree_end, ntrees);
+  if (which != 0 && which != 1) return fail("%s: which = %d (0: training rows, 1: the attached matrix)", who, which);
+  if (which == 1 && !h->d_pred_rm) return fail("%s: no second matrix is attached (gpb_hip_hist_set_pred_bins)", who);
+  if (h->fpad > GPB_TP_MAX_FPAD) return fail("%s: rows of %d columns are wider than the %d bytes a staged row may take", who, h->F, GPB_TP_MAX_FPAD);
+  const int N = which == 0 ? h->n : h->n_pred;
+  if (!rows) cnt = N;
+  if (cnt < 0) return fail("%s: cnt = %d", who, cnt);
+  for (int t = tree_begin; t < tree_end; ++t)
+    if (h->forest_desc[4 * (size_t)t + 1] > 1 && !shap_has_table(h, t))
+      return fail("%s: tree %d has no leaf counts (gpb_hip_hist_forest_set_leaf_counts): the branches a row does not take are weighted by them", who, t);
+  if (rows) {
+    std::vector<unsigned char> listed((size_t)N, 0);
+    for (int i = 0; i < cnt; ++i) {
+      if (rows[i] < 0 || rows[i] >= N) return fail("%s: row index %d (position %d) outside the matrix of %d rows", who, rows[i], i, N);
+      if (listed[(size_t)rows[i]]) return fail("%s: row %d is listed twice (position %d): a row's entries are updated once per call", who, rows[i], i);
+      listed[(size_t)rows[i]] = 1;
+    }
+  }
+  if (cnt == 0) return 0;
+  for (int t = tree_begin; t < tree_end; ++t)                                 // a tree of one leaf needs no counts: its table is its value
+    if (!shap_has_table(h, t) && shap_set_counts(h, who, t, nullptr)) return -1;
+  int emax = 0;
+  for (int t = tree_begin; t < tree_end; ++t) emax = std::max(emax, h->shap_desc[4 * (size_t)t + 2]);
+  if (emax > GPB_SHAP_MAX_UNIQUE || gpb::tree_shap_rows_per_block(h->fpad, emax) == 0) return fail("%s: internal error: %d elements on a path", who, emax);
+  HIP_OK(hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+  gpb::TreeShapArgs a;
+  a.bins_rm = which == 0 ? h->d_bins_rm : h->d_pred_rm; a.fpad = h->fpad; a.F = h->F; a.rows = nullptr; a.cnt = cnt;
+  a.tables = h->d_shap; a.desc = reinterpret_cast<const int4*>(h->d_shap_desc); a.tree_begin = tree_begin; a.tree_end = tree_end;
+  a.ratio = h->d_shap_ratio; a.out = d_out; a.max_unique = emax;
+  if (rows) {                                                                  // the row list's staging buffer is the scoring calls' (same protocol)
+    if (h->prows_pending) { HIP_OK(hipEventSynchronize(h->ev_prows)); h->prows_pending = false; }
+    if (h->prows_cap < cnt) {
+      HIP_OK(hipStreamSynchronize(st));
+      dev_free(h->d_prows); if (h->h_prows) { (void)hipHostFree(h->h_prows); h->h_prows = nullptr; } h->prows_cap = 0;
+      HIP_OK(hipMalloc(&h->d_prows, sizeof(int) * (size_t)cnt));
+      HIP_OK(hipHostMalloc(&h->h_prows, sizeof(int) * (size_t)cnt));
+      h->prows_cap = cnt;
+    }
+    if (!h->ev_prows) HIP_OK(hipEventCreateWithFlags(&h->ev_prows, hipEventDisableTiming));
+    std::copy(rows, rows + cnt, h->h_prows);
+    HIP_OK(hipMemcpyAsync(h->d_prows, h->h_prows, sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, st));
+    HIP_OK(hipEventRecord(h->ev_prows, st));
+    h->prows_pending = true;
+    a.rows = h->d_prows;
+  }
+  HIP_OK(gpb::launch_tree_shap(a, st));
+  if (ms_avg) {      // measurement helper: the launch above was the warm-up; `reps` more of the same launch between two events
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    const auto drop = scope_exit([&] { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); });
+    HIP_OK(hipEventRecord(e0, st));
+    for (int rep = 0; rep < reps; ++rep) HIP_OK(gpb::launch_tree_shap(a, st));
+    HIP_OK(hipEventRecord(e1, st));
+    HIP_OK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    *ms_avg = ms / reps;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int gpb_hip_hist_node_go_left_mask(int32_t max_bin, int32_t default_bin, int32_t most_freq_bin, int32_t missing_type, int32_t default_left,
@@ -610,8 +817,13 @@ extern "C" int gpb_hip_hist_forest_keep_last_tree(gpb_hip_hist_t* h, double shri
   const gpb_hip_hist::LastTree& lt = h->last_tree;
   if (!lt.valid) return fail("gpb_hip_hist_forest_keep_last_tree: no tree has been grown on this handle (gpb_hip_hist_grow_tree)");
   std::vector<int> is_cat(h->tree_node_is_cat.begin(), h->tree_node_is_cat.end());
+  int32_t id = -1;
   if (forest_store(h, "gpb_hip_hist_forest_keep_last_tree", lt.num_leaves, lt.split_feature.data(), lt.threshold.data(), lt.default_left.data(), lt.left_child.data(),
-                   lt.right_child.data(), is_cat.data(), h->tree_node_cat_bits.data(), lt.leaf_value.data(), shrinkage, tree_id)) return -1;
+                   lt.right_child.data(), is_cat.data(), h->tree_node_cat_bits.data(), lt.leaf_value.data(), shrinkage, &id)) return -1;
+  if (tree_id) *tree_id = id;
+  // the tree's own cover counts (the global counts of gpb_hip_hist_grow_tree; with a bag the in-bag counts): its path table for the contributions.  A tree
+  // that cannot have one (a path of more than GPB_SHAP_MAX_UNIQUE distinct columns) is stored all the same: scoring needs no table, a contribution call names it
+  if (lt.num_leaves > 1 && (int)lt.leaf_count.size() == lt.num_leaves) (void)shap_set_counts(h, "gpb_hip_hist_forest_keep_last_tree", id, lt.leaf_count.data());
   API_END();
 }
 
@@ -628,6 +840,7 @@ extern "C" int gpb_hip_hist_forest_clear(gpb_hip_hist_t* h) {
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
   h->forest_words.clear(); h->forest_desc.clear();
+  h->shap_words.clear(); h->shap_desc.clear(); h->shap_expected.clear();
   API_END();
 }
 
@@ -687,6 +900,74 @@ extern "C" int gpb_hip_hist_add_score(gpb_hip_hist_t* h, int32_t which, int32_t 
   HIP_OK(hipMemcpyAsync(h->d_pscore, score, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, h->stream));
   if (tree_predict_impl(h, "gpb_hip_hist_add_score", which, tree_begin, tree_end, rows, cnt, h->d_pscore, nullptr)) { (void)hipStreamSynchronize(h->stream); return -1; }
   HIP_OK(hipMemcpyAsync(score, h->d_pscore, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  API_END();
+}
+
+extern "C" int gpb_hip_tree_shap_paths(int32_t num_leaves, const int32_t* split_feature_inner, const int32_t* left_child, const int32_t* right_child,
+                                       const uint32_t* node_sets8, const int32_t* leaf_count, int32_t elem_cap, int32_t* leaf_first, int32_t* elem_column,
+                                       uint32_t* elem_set8, double* elem_zero) {
+  API_BEGIN();
+  if (!leaf_first || elem_cap < 0 || (elem_cap > 0 && (!elem_column || !elem_set8 || !elem_zero))) return fail("gpb_hip_tree_shap_paths: null argument");
+  std::vector<int> first; std::vector<ShapElem> elems;
+  if (tree_shap_paths("gpb_hip_tree_shap_paths", num_leaves, split_feature_inner, left_child, right_child, node_sets8, leaf_count, &first, &elems)) return -1;
+  if ((int)elems.size() > elem_cap) return fail("gpb_hip_tree_shap_paths: the table has %d elements, the output arrays hold %d", (int)elems.size(), elem_cap);
+  std::copy(first.begin(), first.end(), leaf_first);
+  for (size_t e = 0; e < elems.size(); ++e) {
+    elem_column[e] = elems[e].col; elem_zero[e] = elems[e].zero;
+    std::copy(elems[e].set, elems[e].set + 8, elem_set8 + 8 * e);
+  }
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_set_leaf_counts(gpb_hip_hist_t* h, int32_t tree_id, const int32_t* leaf_count) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (shap_set_counts(h, "gpb_hip_hist_forest_set_leaf_counts", tree_id, leaf_count)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_tree_expected_value(gpb_hip_hist_t* h, int32_t tree_id, double* expected_value) {
+  API_BEGIN();
+  if (!h || !expected_value) return fail("null argument");
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  if (tree_id < 0 || tree_id >= ntrees) return fail("gpb_hip_hist_tree_expected_value: tree %d: the forest holds %d (unknown tree id)", tree_id, ntrees);
+  if (shap_has_table(h, tree_id)) { *expected_value = h->shap_expected[(size_t)tree_id]; return 0; }
+  if (h->forest_desc[4 * (size_t)tree_id + 1] > 1) return fail("gpb_hip_hist_tree_expected_value: tree %d has no leaf counts (gpb_hip_hist_forest_set_leaf_counts)", tree_id);
+  std::memcpy(expected_value, h->forest_words.data() + (size_t)h->forest_desc[4 * (size_t)tree_id], sizeof(double));      // one leaf: its stored value
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_contrib_dev(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt, void* out_dev) {
+  API_BEGIN();
+  if (!h || !out_dev) return fail("null argument");
+  if (tree_shap_impl(h, "gpb_hip_hist_add_contrib_dev", which, tree_begin, tree_end, rows, cnt, static_cast<double*>(out_dev))) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_contrib_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt, void* out_dev,
+                                              int32_t reps, double* ms_avg) {
+  API_BEGIN();
+  if (!h || !out_dev || !ms_avg || reps < 1) return fail("invalid argument");
+  if (tree_shap_impl(h, "gpb_hip_hist_add_contrib_bench", which, tree_begin, tree_end, rows, cnt, static_cast<double*>(out_dev), reps, ms_avg)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_add_contrib(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt, double* out) {
+  API_BEGIN();
+  if (!h || !out) return fail("null argument");
+  if (which == 1 && !h->d_pred_rm) return fail("gpb_hip_hist_add_contrib: no second matrix is attached (gpb_hip_hist_set_pred_bins)");
+  if (which != 0 && which != 1) return fail("gpb_hip_hist_add_contrib: which = %d (0: training rows, 1: the attached matrix)", which);
+  const size_t len = (size_t)(which == 0 ? h->n : h->n_pred) * (size_t)(h->F + 1);
+  HIP_OK(hipSetDevice(h->device));
+  if (h->pcontrib_cap < len) {
+    HIP_OK(hipStreamSynchronize(h->stream));
+    dev_free(h->d_pcontrib); h->pcontrib_cap = 0;
+    HIP_OK(hipMalloc(&h->d_pcontrib, sizeof(double) * len)); h->pcontrib_cap = len;
+  }
+  HIP_OK(hipMemcpyAsync(h->d_pcontrib, out, sizeof(double) * len, hipMemcpyHostToDevice, h->stream));
+  if (tree_shap_impl(h, "gpb_hip_hist_add_contrib", which, tree_begin, tree_end, rows, cnt, h->d_pcontrib)) { (void)hipStreamSynchronize(h->stream); return -1; }
+  HIP_OK(hipMemcpyAsync(out, h->d_pcontrib, sizeof(double) * len, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   API_END();
 }

@@ -891,6 +891,8 @@ class HistBuilder(object):
         _shim_call(_lib().gpb_hip_hist_forest_add_tree(self.h, C.c_int(k), _p(ia["split_feature_inner"], C.c_int), _p(thr, C.c_uint32), _p(ia["default_left"], C.c_int),
                                                        _p(ia["left_child"], C.c_int), _p(ia["right_child"], C.c_int), _p(nic, C.c_int), _p(ncb, C.c_uint32), _p(lv),
                                                        C.c_double(shrinkage), C.byref(tid)))
+        if k > 1 and tree.get("leaf_count") is not None:         # the cover counts the contributions need (the tree itself is stored either way)
+            self.set_leaf_counts(tid.value, tree["leaf_count"])
         return tid.value
 
     def keep_last_tree(self, shrinkage=1.0):
@@ -972,6 +974,79 @@ class HistBuilder(object):
         _shim_call(_lib().gpb_hip_hist_add_score_bench(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
                                                        C.c_void_p(int(score_dev_ptr)), C.c_int(int(reps)), C.byref(ms)))
         return ms.value
+
+    # ---- per-feature contributions (TreeSHAP) of the stored trees ----
+    @staticmethod
+    def tree_shap_paths(tree, node_sets, leaf_count=None):
+        """-> (first (num_leaves + 1), column, sets (E, 8) uint32, zero_fraction): per leaf the distinct columns on its path in order of first appearance, each
+        with the set of stored bins that keep a row on the path and the product of count(child) / count(node).  node_sets: (nodes, 8) go-left sets
+        (node_go_left_mask).  Host only: needs no handle and no device; the device path is built by the same function."""
+        k = int(tree["num_leaves"])
+        nn = max(k - 1, 0)
+        ia = [np.ascontiguousarray(np.asarray(tree[key])[:nn], dtype=np.int32) for key in ("split_feature_inner", "left_child", "right_child")]
+        ns = np.ascontiguousarray(np.asarray(node_sets, dtype=np.uint32).reshape(-1, 8)[:nn])
+        lc = tree.get("leaf_count") if leaf_count is None else leaf_count
+        lc = None if lc is None else np.ascontiguousarray(np.asarray(lc)[:k], dtype=np.int32)
+        cap = 32 * k
+        first = np.zeros(k + 1, dtype=np.int32); col = np.zeros(cap, dtype=np.int32); sets = np.zeros((cap, 8), dtype=np.uint32); zero = np.zeros(cap)
+        _shim_call(_lib().gpb_hip_tree_shap_paths(C.c_int(k), _p(ia[0], C.c_int), _p(ia[1], C.c_int), _p(ia[2], C.c_int), _p(ns, C.c_uint32), _p(lc, C.c_int),
+                                                  C.c_int(cap), _p(first, C.c_int), _p(col, C.c_int), _p(sets, C.c_uint32), _p(zero)))
+        e = int(first[-1])
+        return first, col[:e].copy(), sets[:e].copy(), zero[:e].copy()
+
+    def set_leaf_counts(self, tree_id, leaf_count):
+        """The cover counts of a stored tree, one per leaf (the reference's leaf_count; a node's count is the sum below it): TreeSHAP weights the branches a
+        row does not take by them.  keep_last_tree records the grown tree's own counts, add_tree a dict's 'leaf_count'."""
+        lc = np.ascontiguousarray(leaf_count, dtype=np.int32)
+        _shim_call(_lib().gpb_hip_hist_forest_set_leaf_counts(self.h, C.c_int(int(tree_id)), _p(lc, C.c_int)))
+
+    def tree_expected_value(self, tree_id):
+        """sum over the leaves of (count / total) * stored leaf value, in leaf order (Tree::ExpectedValue); a tree of one leaf: its value."""
+        v = C.c_double(0)
+        _shim_call(_lib().gpb_hip_hist_tree_expected_value(self.h, C.c_int(int(tree_id)), C.byref(v)))
+        return v.value
+
+    def add_contrib(self, out, trees=None, rows=None, pred=False):
+        """out (float64, (rows of the matrix, F + 1)) += the per-feature contributions of the stored trees `trees` (None: all; an id; (begin, end)) for the
+        listed rows (None: all; any order, no row twice), in place: column f < F gets phi_f, column F the trees' expected values.  A row's entries receive
+        their additions in (tree, leaf, path element) order onto the running value."""
+        n, r, cnt = self._score_rows(rows, pred)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable):
+            raise GPBoostError("add_contrib: out must be a writable contiguous float64 array (it is updated in place)")
+        if out.shape != (n, self.F + 1) and not (pred and n == 0):
+            raise GPBoostError("add_contrib: out must have the shape (rows of the matrix, F + 1) = (%d, %d)" % (n, self.F + 1))
+        t0, t1 = self._tree_range(trees)
+        if r is not None and cnt == 0:
+            return out
+        _shim_call(_lib().gpb_hip_hist_add_contrib(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(out)))
+        return out
+
+    def add_contrib_dev(self, out_dev_ptr, trees=None, rows=None, pred=False):
+        """add_contrib on a device matrix (rows of the matrix x (F + 1) doubles, row-major), enqueued on the handle's stream: nothing is copied and nothing
+        waited for; sync() waits for the stream."""
+        n, r, cnt = self._score_rows(rows, pred)
+        t0, t1 = self._tree_range(trees)
+        if r is not None and cnt == 0:
+            return
+        _shim_call(_lib().gpb_hip_hist_add_contrib_dev(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+                                                       C.c_void_p(int(out_dev_ptr))))
+
+    def add_contrib_bench(self, out_dev_ptr, trees=None, rows=None, pred=False, reps=20):
+        """mean ms of one add_contrib_dev launch (HIP events; one warm-up launch first).  The matrix ends up with reps + 1 updates."""
+        n, r, cnt = self._score_rows(rows, pred)
+        t0, t1 = self._tree_range(trees)
+        ms = C.c_double(0)
+        _shim_call(_lib().gpb_hip_hist_add_contrib_bench(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+                                                         C.c_void_p(int(out_dev_ptr)), C.c_int(int(reps)), C.byref(ms)))
+        return ms.value
+
+    def pred_contrib(self, trees=None, rows=None, pred=False):
+        """-> a fresh (cnt, F + 1) array in list order: the contributions of the stored trees to the listed rows (None: all) -- the shape of the reference's
+        predict(..., pred_contrib=True) for one class."""
+        n, r, cnt = self._score_rows(rows, pred)
+        out = np.zeros((n, self.F + 1))
+        self.add_contrib(out, trees=trees, rows=r, pred=pred)
+        return out if r is None else out[r].copy()
 
     def sync(self):
         _shim_call(_lib().gpb_hip_hist_sync(self.h))

@@ -822,6 +822,42 @@ GPB_HIP_EXPORT int gpb_hip_hist_sync(gpb_hip_hist_t* h);
 GPB_HIP_EXPORT int gpb_hip_hist_add_score_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
                                                 double* score_dev, int32_t reps, double* ms_avg);
 
+/* Per-feature contributions (TreeSHAP) of stored trees on the device: out[row][f] += phi_f of every tree of the range, out[row][F] += the trees' expected values
+ * -- the matrix of the reference's predict(..., pred_contrib=True) for one class, on BINNED rows.  Stands in for Tree::PredictContrib -> the recursive
+ * Tree::TreeSHAP (src/LightGBM/io/tree.cpp:827-998).  The recursion's unique path is compiled per leaf on the host when a tree's cover counts arrive:
+ * the DISTINCT columns on the root-to-leaf path in order of first appearance, each one ELEMENT {column, the 256-bit set of stored bins that keep a row on the
+ * path at every node of that column (AND of the nodes' go-left sets, complemented for right turns), zero fraction = product of count(child) / count(node) over
+ * those nodes, multiplied in double root to leaf}.  A row's one fraction of an element is 1 when its stored bin is in the set, else 0.
+ *   tree_shap_paths        host only, no handle, no device: the table of one tree given as arrays (node_sets8: 8 words per node, e.g. of node_go_left_mask).
+ *                          leaf_first: num_leaves + 1 entries; per element its column, 8 words and zero fraction (elem_cap: the room in those arrays; at most
+ *                          32 * num_leaves are needed).  The device path is built by the same function.  Refused: a leaf count < 1, a path of more than 32
+ *                          distinct columns (the permutation weights lose about two digits per 8 further columns; the message names the leaf and the
+ *                          number), an invalid tree.  num_leaves = 1: no elements, leaf_count may be NULL.
+ *   forest_set_leaf_counts the cover counts of the stored tree tree_id, one per leaf (count of a node = sum of the leaf counts below it: the reference's
+ *                          internal_count_ after training); compiles and uploads the tree's path table.  forest_keep_last_tree does this itself with the
+ *                          counts gpb_hip_hist_grow_tree returned (with a bag: the in-bag counts, as in the reference); a grown tree whose table is
+ *                          refused is stored without one.  A tree of one leaf needs no counts.
+ *   tree_expected_value    sum over the leaves, in leaf order, of (count / total) * stored leaf value (Tree::ExpectedValue); one leaf: its value
+ *   add_contrib            out: HOST matrix, rows of the matrix `which` x (F + 1), row-major, updated in place for the listed rows (rows == NULL: all; any
+ *                          order; a row listed twice is refused).  A row's F + 1 entries receive their additions strictly in (tree, leaf, element) order onto
+ *                          the value that was there, in fp64 without fused multiply-adds: the bits do not depend on the other rows of the call or on how a
+ *                          range of trees is split over consecutive calls.  Entries of rows not listed keep their bits.
+ *   add_contrib_dev        the same with out a DEVICE matrix, enqueued on the handle's stream: no copy of out and no wait (as add_score_dev)
+ *   add_contrib_bench      measurement helper: one launch as warm-up, then `reps` more between two HIP events; *ms_avg = their mean
+ * Refusals, each -1 with a message before any kernel is launched: a tree of the range with more than one leaf and no counts ("has no leaf counts"), and those
+ * of the scoring calls in their wording (unknown tree id or empty range, a row outside the matrix, no second matrix, rows wider than 560 padded columns). */
+GPB_HIP_EXPORT int gpb_hip_tree_shap_paths(int32_t num_leaves, const int32_t* split_feature_inner, const int32_t* left_child, const int32_t* right_child,
+                                           const uint32_t* node_sets8, const int32_t* leaf_count, int32_t elem_cap, int32_t* leaf_first, int32_t* elem_column,
+                                           uint32_t* elem_set8, double* elem_zero);
+GPB_HIP_EXPORT int gpb_hip_hist_forest_set_leaf_counts(gpb_hip_hist_t* h, int32_t tree_id, const int32_t* leaf_count);
+GPB_HIP_EXPORT int gpb_hip_hist_tree_expected_value(gpb_hip_hist_t* h, int32_t tree_id, double* expected_value);
+GPB_HIP_EXPORT int gpb_hip_hist_add_contrib(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                            double* out);
+GPB_HIP_EXPORT int gpb_hip_hist_add_contrib_dev(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                                void* out_dev);
+GPB_HIP_EXPORT int gpb_hip_hist_add_contrib_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
+                                                  void* out_dev, int32_t reps, double* ms_avg);
+
 #ifdef __cplusplus
 }
 #endif
