@@ -294,8 +294,9 @@ static int comm_reducescatter_i64(GpbComm& c, const long long* send, long long* 
 // costs ~24 us with ONE rank in the loop (launch of the collective kernel + the publish kernel behind it) -- the largest term outside the shard
 // kernel at N = 8.  The sums do not need a device collective at all: every rank's finisher workgroup already stores them
 // straight into pinned host memory with system-scope stores ("the data is the flag", vecchia_kernels.hip: vecchia_finish) and its host polls
-// for them.  The mailbox makes that pinned buffer a POSIX shared-memory segment mapped by every rank of the node: rank r's GPU writes slot r,
-// every host polls all `world` slots and adds them IN RANK ORDER -- the same bits on every rank, no collective launch, no second kernel, no
+// for them.  The mailbox adds a POSIX shared-memory segment mapped by every rank of the node: rank r's host copies its sums from its own pinned
+// buffer (hipHostMalloc: the device never addresses the segment, which would need a page-lock of mapped memory) into slot r the moment they
+// arrive, every host polls all `world` slots and adds them IN RANK ORDER -- the same bits on every rank, no collective launch, no second kernel, no
 // peer access; the cross-rank step is the hosts' cache coherence.  Layout: header {magic, world, ready[world]}, then [3 generations][world][8]
 // doubles.  Generation g = evaluation count % 3; at the start of evaluation e a rank re-arms ITS OWN slot of generation (e + 1) % 3 with the
 // sentinel: no rank can still be reading that generation (it was read in evaluation e - 2, and a rank only starts evaluation e after every
@@ -303,7 +304,6 @@ static int comm_reducescatter_i64(GpbComm& c, const long long* send, long long* 
 struct GpbMailbox {
   int world = 0, rank = -1;
   void* base = nullptr; size_t bytes = 0;
-  double* dev_base = nullptr;                 // device address of the mapping (hipHostGetDevicePointer)
   unsigned long long evals = 0;
   bool dead = false;                          // an evaluation failed or timed out on this rank: the generation counters of the ranks may be out of step, nothing more goes through it
   char name[64] = "";
@@ -321,12 +321,9 @@ struct GpbMailbox {
   volatile unsigned long long* slot(int gen, int r) const {
     return reinterpret_cast<volatile unsigned long long*>(static_cast<char*>(base) + header_bytes(world)) + ((size_t)gen * world + r) * 8;
   }
-  double* dev_slot(int gen, int r) const {
-    return reinterpret_cast<double*>(reinterpret_cast<char*>(dev_base) + header_bytes(world)) + ((size_t)gen * world + r) * 8;
-  }
   void release() {
-    if (base) { (void)hipHostUnregister(base); (void)munmap(base, bytes); }
-    base = nullptr; dev_base = nullptr; world = 0; rank = -1; bytes = 0; evals = 0; dead = false;
+    if (base) (void)munmap(base, bytes);
+    base = nullptr; world = 0; rank = -1; bytes = 0; evals = 0; dead = false;
   }
 };
 
@@ -911,7 +908,7 @@ static int sorted_gather_prepare(gpb_hip_vecchia_t* h) {
 }
 
 static int vecchia_launch(gpb_hip_vecchia_t* h, int mode, int cov_type, double var, double a, int gauss, double* out_dev,
-                          int nout, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, double* host_slot_dev = nullptr) {
+                          int nout, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   if (!h) return fail("null handle");
   if (!h->has_nn) return fail("neighbours have not been determined (call gpb_hip_vecchia_find_neighbors / _set_neighbors)");
   if (!h->has_y) return fail("response data has not been set (call gpb_hip_vecchia_set_y)");
@@ -952,12 +949,12 @@ static int vecchia_launch(gpb_hip_vecchia_t* h, int mode, int cov_type, double v
     HIP_OK(gpb::launch_vecchia_point_big(mode, cov_type, h->d > 3 ? 0 : (h->d == 3 ? 3 : 2), k, h->stream));
     if (ev1) HIP_OK(hipEventRecord(ev1, h->stream));
     HIP_OK(gpb::launch_reduce_partials(h->d_partials, h->i_end - h->i_begin, mode == gpb::MODE_GRAD ? GPB_NUM_PARTIALS : 3, h->d_out, out_dev, h->stream,
-                                       host_slot_dev ? host_slot_dev : h->h_out));
+                                       h->h_out));
   } else {
     // ONE launch per evaluation: persistent worker workgroups + a finisher workgroup that adds up their sums (vecchia_kernels.hip)
     k.ngroups = (h->i_end - h->i_begin + 15) / 16;
     k.max_workers = h->worker_cap;
-    k.out = h->d_out; k.out_user = out_dev; k.out_host = host_slot_dev ? host_slot_dev : h->h_out;
+    k.out = h->d_out; k.out_user = out_dev; k.out_host = h->h_out;
     HIP_OK(gpb::launch_vecchia_point_kernel(mode, cov_type, h->d == 3, k, h->stream));
     if (ev1) HIP_OK(hipEventRecord(ev1, h->stream));
   }
@@ -1107,7 +1104,7 @@ int gpb_hip_mailbox_create(int world, char* name_out64) {
   std::strncpy(name_out64, name, 63);
   API_END();
 }
-// every rank (rank 0 included): map the segment, page-lock it for this rank's device, arm the own slots, wait until all ranks have done so;
+// every rank (rank 0 included): map the segment, arm the own slots, wait until all ranks have done so;
 // the name is unlinked once everybody is attached (the mappings keep the segment alive)
 int gpb_hip_vecchia_mailbox_attach(gpb_hip_vecchia_t* h, const char* name, int rank, int world) {
   API_BEGIN();
@@ -1127,13 +1124,8 @@ int gpb_hip_vecchia_mailbox_attach(gpb_hip_vecchia_t* h, const char* name, int r
   if (p == MAP_FAILED) { (void)shm_unlink(name); return fail("gpb_hip_vecchia_mailbox_attach: mmap failed: %s", std::strerror(errno)); }
   auto* hdr = static_cast<volatile unsigned long long*>(p);
   if (hdr[0] != GpbMailbox::kMagic || hdr[1] != (unsigned long long)world) { (void)munmap(p, bytes); (void)shm_unlink(name); return fail("gpb_hip_vecchia_mailbox_attach: %s is not a mailbox for %d ranks", name, world); }
-  hipError_t e = hipHostRegister(p, bytes, hipHostRegisterMapped);
-  if (e != hipSuccess) { (void)munmap(p, bytes); (void)shm_unlink(name); return fail("hipHostRegister of the mailbox failed: %s", hipGetErrorString(e)); }
-  void* dp = nullptr;
-  e = hipHostGetDevicePointer(&dp, p, 0);
-  if (e != hipSuccess) { (void)hipHostUnregister(p); (void)munmap(p, bytes); (void)shm_unlink(name); return fail("hipHostGetDevicePointer of the mailbox failed: %s", hipGetErrorString(e)); }
   GpbMailbox& mb = h->mbox;
-  mb.base = p; mb.bytes = bytes; mb.dev_base = static_cast<double*>(dp); mb.world = world; mb.rank = rank; mb.evals = 0;
+  mb.base = p; mb.bytes = bytes; mb.world = world; mb.rank = rank; mb.evals = 0;
   std::strncpy(mb.name, name, sizeof(mb.name) - 1);
   for (int g = 0; g < 3; ++g) for (int t = 0; t < 8; ++t) mb.slot(g, rank)[t] = kFetchSentinel;
   std::atomic_thread_fence(std::memory_order_release);
@@ -1180,15 +1172,27 @@ static int vecchia_mailbox_terms(gpb_hip_vecchia_t* h, int mode, int cov_type, d
   const int gen = (int)(e % 3), next = (int)((e + 1) % 3);
   for (int t = 0; t < 8; ++t) mb.slot(next, mb.rank)[t] = kFetchSentinel;       // re-arm the own slot of the generation after this one (see GpbMailbox)
   std::atomic_thread_fence(std::memory_order_release);
-  if (vecchia_launch(h, mode, cov_type, var, a, gauss, nullptr, nout, nullptr, nullptr, mb.dev_slot(gen, mb.rank))) { mb.dead = true; return -1; }
+  if (vecchia_launch(h, mode, cov_type, var, a, gauss, nullptr, nout)) { mb.dead = true; return -1; }
   mb.evals = e;
   h->launches_unfetched = 0;
   const int nterms = nout > 3 ? GPB_NUM_PARTIALS : 3;
   const double limit_s = GpbMailbox::env_seconds("GPB_MAILBOX_TIMEOUT_S", 30.0);
   const auto t0 = std::chrono::steady_clock::now();
-  bool own_synced = false;
+  const volatile unsigned long long* own = reinterpret_cast<const volatile unsigned long long*>(h->h_out);   // armed by vecchia_launch
+  bool own_synced = false, own_published = false;
   for (unsigned spin = 0;; ++spin) {
-    bool all = true;
+    if (!own_published) {                                    // this rank's sums have arrived in its pinned buffer: hand them to the peers
+      bool mine = true;
+      for (int t = 0; t < nterms; ++t) mine = mine && own[t] != kFetchSentinel;
+      if (mine) {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        volatile unsigned long long* v = mb.slot(gen, mb.rank);
+        for (int t = 0; t < nterms; ++t) v[t] = own[t];
+        std::atomic_thread_fence(std::memory_order_release);
+        own_published = true;
+      }
+    }
+    bool all = own_published;
     for (int r = 0; r < mb.world && all; ++r) {
       const volatile unsigned long long* v = mb.slot(gen, r);
       for (int t = 0; t < nterms; ++t) all = all && v[t] != kFetchSentinel;

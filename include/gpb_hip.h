@@ -222,8 +222,9 @@ GPB_HIP_EXPORT int gpb_hip_route_b_get_device_search(void);
 GPB_HIP_EXPORT int gpb_hip_vecchia_timing(gpb_hip_vecchia_t* h, int enable, int64_t* launches, double* mean_kernel_ms);
 
 /* Node-local MAILBOX for the 3 / 7 sums of a sharded likelihood / gradient evaluation: a POSIX
- * shared-memory segment mapped and page-locked by every rank of the node.  Each rank's finisher workgroup stores its shard sums straight into its
- * slot (system-scope stores, no collective kernel, no copy), every host polls all slots and adds them in rank order: identical bits on all ranks.
+ * shared-memory segment mapped by every rank of the node.  Each rank's finisher workgroup stores its shard sums straight into the rank's pinned
+ * host buffer (system-scope stores, no collective kernel, no copy on the stream), its host moves them into its slot of the segment as soon as they
+ * arrive, every host polls all slots and adds them in rank order: identical bits on all ranks.
  * With a mailbox attached, gpb_hip_vecchia_{nll,grad}_terms_allreduce use it instead of ncclAllReduce; RCCL stays for y_aux, histograms and the
  * neighbour table.  Every rank must make the same sequence of evaluations (SPMD), as with any collective.
  *   gpb_hip_mailbox_create          rank 0: creates the segment for `world` ranks, returns its name (64 bytes; hand it to the other ranks)

@@ -1,6 +1,6 @@
 """The node-local mailbox ACROSS PROCESSES: `world` separate processes -- one HIP context each, all on device 0 because a box of
-the pool has one GPU; RCCL is not involved -- shard one Vecchia evaluation, every process's finisher workgroup writes its 3 / 7 sums into the shared-memory
-segment (shm_open + hipHostRegister in every process), every host polls all slots.  Checks: all ranks return identical bits; the job's sums equal the
+the pool has one GPU; RCCL is not involved -- shard one Vecchia evaluation, every process's finisher workgroup writes its 3 / 7 sums into the process's pinned
+buffer, its host moves them into the shared-memory segment (shm_open + mmap in every process), every host polls all slots.  Checks: all ranks return identical bits; the job's sums equal the
 ranks' shard sums added in rank order, bit for bit; they agree with the unsharded evaluation to 1e-12.  Reports the time per evaluation.
 (The in-process rank groups of tests/test_multirank_gpu.py exercise the same protocol inside one process; this is the form bench.py --gpus N uses.)
     python scripts/gpu_mailbox_multiprocess.py [world ...]        default: 2 4"""
