@@ -34,6 +34,7 @@
 #include "nn_kernels.h"
 #include "tree_predict_kernels.h"
 #include "tree_shap_kernels.h"
+#include "tree_raw_kernels.h"
 #include "vecchia_kernels.h"
 #include "vif_kernels.h"
 #include <fcntl.h>
@@ -476,6 +477,11 @@ struct gpb_hip_hist {
   std::vector<uint32_t> shap_words; std::vector<int> shap_desc; std::vector<double> shap_expected;
   uint32_t* d_shap = nullptr; size_t shap_cap_words = 0; int* d_shap_desc = nullptr; int shap_cap_trees = 0; double* d_shap_ratio = nullptr;
   double* d_pcontrib = nullptr; size_t pcontrib_cap = 0;
+  // scoring on raw feature values (gpb_tree.inc; tree_raw_kernels.h): the raw forms of the stored trees that have a raw rule, in the order the rules arrived;
+  // desc: 4 ints per tree {first word, num_leaves, stored bytes (0: no raw rule), bitset words}; the attached raw matrix (owned copy or borrowed pointer)
+  std::vector<uint32_t> rawf_words; std::vector<int> rawf_desc;
+  uint32_t* d_rawf = nullptr; size_t rawf_cap_words = 0; int* d_rawf_desc = nullptr; int rawf_cap_trees = 0;
+  void* d_pred_raw = nullptr; bool pred_raw_owned = false; int n_raw = 0; int raw_dtype = 0; long long raw_stride = 0;
 };
 
 // column-major n x d coordinates -> the kernels' records {x0, x1, x2, 0} (the coordinates beyond the third travel in d_coords_nd)
@@ -2134,6 +2140,8 @@ int gpb_hip_hist_free(gpb_hip_hist_t* h) {
   h->comm.release(); dev_free(h->d_limbs);
   dev_free(h->d_forest); dev_free(h->d_forest_desc); dev_free(h->d_pred_rm); dev_free(h->d_prows); dev_free(h->d_pscore); dev_free(h->d_pleaf);
   dev_free(h->d_shap); dev_free(h->d_shap_desc); dev_free(h->d_shap_ratio); dev_free(h->d_pcontrib);
+  dev_free(h->d_rawf); dev_free(h->d_rawf_desc);
+  if (h->pred_raw_owned) dev_free(h->d_pred_raw);
   if (h->h_prows) (void)hipHostFree(h->h_prows);
   if (h->ev_prows) (void)hipEventDestroy(h->ev_prows);
   delete h;

@@ -497,16 +497,105 @@ int forest_store(gpb_hip_hist_t* h, const char* who, int num_leaves, const int32
   return 0;
 }
 
+// ---- the raw rule of a stored tree: Tree::Decision on feature values (include/LightGBM/tree.h:329-401; tree_raw_kernels.h) ---------------------------------------
+bool raw_has_rule(const gpb_hip_hist_t* h, int t) { return 4 * (size_t)t + 3 < h->rawf_desc.size() && h->rawf_desc[4 * (size_t)t + 2] > 0; }
+
+// validate the rule of the stored tree tree_id, compile its raw form (columns, children and leaf values are the bin form's), append it and bring the device copy up
+// to date.  threshold / decision_type: one per node; a categorical node's threshold is its index into cat_boundaries (num_cat + 1 entries, words of cat_threshold).
+int raw_set_rule(gpb_hip_hist_t* h, const char* who, int tree_id, const double* threshold, const int8_t* decision_type, int num_cat, const int32_t* cat_boundaries,
+                 const uint32_t* cat_threshold) {
+  const int ntrees = (int)(h->forest_desc.size() / 4);
+  if (tree_id < 0 || tree_id >= ntrees) return fail("%s: tree %d: the forest holds %d (unknown tree id)", who, tree_id, ntrees);
+  const int nl = h->forest_desc[4 * (size_t)tree_id + 1], nn = nl - 1;
+  if (nn > 0 && (!threshold || !decision_type)) return fail("%s: null argument", who);
+  if (num_cat < 0 || (num_cat > 0 && (!cat_boundaries || !cat_threshold))) return fail("%s: num_cat = %d without boundaries and bitsets", who, num_cat);
+  if (num_cat > 0 && cat_boundaries[0] < 0) return fail("%s: cat_boundaries[0] = %d (boundaries are ascending from 0)", who, cat_boundaries[0]);
+  for (int k = 0; k < num_cat; ++k)
+    if (cat_boundaries[k + 1] <= cat_boundaries[k])
+      return fail("%s: cat_boundaries not ascending: entry %d is %d after %d", who, k + 1, cat_boundaries[k + 1], cat_boundaries[k]);
+  const uint32_t* bw = h->forest_words.data() + (size_t)h->forest_desc[4 * (size_t)tree_id];      // the bin form: columns, children, leaf values
+  std::vector<int> first((size_t)nn, 0), words((size_t)nn, 0);
+  long long nsets = 0;
+  for (int i = 0; i < nn; ++i) {
+    const int dt = decision_type[i], mt = (dt >> 2) & 3;
+    if (mt == 3) return fail("%s: node %d has the missing type 3 (0: None, 1: Zero, 2: NaN)", who, i);
+    if (dt & 1) {
+      const double c = threshold[i];
+      if (!(c >= 0.0 && c < (double)num_cat) || c != std::floor(c))
+        return fail("%s: categorical node %d has the index %g outside num_cat = %d", who, i, c, num_cat);
+      first[(size_t)i] = (int)nsets; words[(size_t)i] = cat_boundaries[(int)c + 1] - cat_boundaries[(int)c];
+      nsets += words[(size_t)i];
+    } else if (!std::isfinite(threshold[i])) {
+      return fail("%s: node %d has the non-finite threshold %g", who, i, threshold[i]);
+    }
+    if ((long long)nn * GPB_TR_NODE_BYTES + 4 * nsets + 8LL * nl > GPB_TR_CHUNK_BYTES) break;           // (refused below, whatever the later nodes hold)
+  }
+  const long long bytes = (long long)nn * GPB_TR_NODE_BYTES + (nsets + 1) / 2 * 8 + 8LL * nl;
+  if (bytes > GPB_TR_CHUNK_BYTES)
+    return fail("%s: the raw form of tree %d (%d leaves, %lld bitset words: %lld bytes or more) does not fit the %d bytes of LDS a chunk of trees may take", who,
+                tree_id, nl, nsets, bytes, GPB_TR_CHUNK_BYTES);
+  const int sw = (int)((nsets + 1) / 2 * 2), tb = gpb::tree_raw_tree_bytes(nl, (int)nsets);
+  const size_t w0 = h->rawf_words.size();
+  if (w0 + (size_t)tb / 4 > (size_t)0x7fffffff) return fail("%s: the raw forest is full", who);
+  h->rawf_words.resize(w0 + (size_t)tb / 4, 0u);
+  uint32_t* w = h->rawf_words.data() + w0;
+  uint32_t* sets = w + (size_t)nn * (GPB_TR_NODE_BYTES / 4);
+  for (int i = 0; i < nn; ++i) {
+    const uint32_t* bn = bw + (size_t)i * GPB_TP_NODE_WORDS + 8;       // {column, left child, right child}
+    const int dt = decision_type[i];
+    const bool cat = (dt & 1) != 0;
+    int flags = ((dt >> 2) & 3) | ((dt & 2) ? GPB_TR_FLAG_DEFAULT_LEFT : 0);
+    double thr = threshold[i];
+    if (cat) {
+      flags |= GPB_TR_FLAG_CATEGORICAL | (words[(size_t)i] << GPB_TR_CAT_WORDS_SHIFT) | (int)((unsigned)first[(size_t)i] << GPB_TR_CAT_FIRST_SHIFT);
+      std::copy(cat_threshold + cat_boundaries[(int)thr], cat_threshold + cat_boundaries[(int)thr + 1], sets + first[(size_t)i]);
+    }
+    uint32_t* nd = w + (size_t)i * (GPB_TR_NODE_BYTES / 4);
+    std::memcpy(nd, &thr, sizeof(double));
+    nd[2] = bn[0]; nd[3] = bn[1]; nd[4] = bn[2]; nd[5] = (uint32_t)flags;
+  }
+  std::memcpy(sets + sw, bw + (size_t)nn * GPB_TP_NODE_WORDS, sizeof(double) * (size_t)nl);      // leaf_value * shrinkage, as stored
+  h->rawf_desc.resize(4 * (size_t)ntrees, 0);
+  const int desc[4] = {(int)w0, nl, tb, sw};
+  std::copy(desc, desc + 4, h->rawf_desc.begin() + 4 * (size_t)tree_id);
+  // device copy: no scoring kernel is reading the buffers; they grow by doubling; the new form and the (small) descriptor array are uploaded
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  size_t from = w0;
+  if (h->rawf_words.size() > h->rawf_cap_words) {
+    const size_t cw = std::max<size_t>(2 * h->rawf_words.size(), 1u << 14);
+    dev_free(h->d_rawf); h->rawf_cap_words = 0;
+    HIP_OK(hipMalloc(&h->d_rawf, sizeof(uint32_t) * cw));
+    h->rawf_cap_words = cw; from = 0;
+  }
+  if (ntrees > h->rawf_cap_trees) {
+    const int ct = std::max(2 * ntrees, 64);
+    dev_free(h->d_rawf_desc); h->rawf_cap_trees = 0;
+    HIP_OK(hipMalloc(&h->d_rawf_desc, sizeof(int) * 4 * (size_t)ct));
+    h->rawf_cap_trees = ct;
+  }
+  HIP_OK(hipMemcpy(h->d_rawf + from, h->rawf_words.data() + from, sizeof(uint32_t) * (h->rawf_words.size() - from), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->d_rawf_desc, h->rawf_desc.data(), sizeof(int) * h->rawf_desc.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
 // One scoring call.  rows: HOST indices into the matrix `which` (nullptr: all its rows).  Exactly one of d_score (device, all rows of the matrix) / leaf_out_host.
 int tree_predict_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_begin, int tree_end, const int32_t* rows, int cnt, double* d_score,
                       int32_t* leaf_out_host, int reps = 0, double* ms_avg = nullptr) {
   const int ntrees = (int)(h->forest_desc.size() / 4);
   if (tree_begin < 0 || tree_end > ntrees || tree_begin >= tree_end)
     return fail("%s: trees [%d, %d): the forest holds %d (unknown tree id or empty range)", who, tree_begin, tree_end, ntrees);
-  if (which != 0 && which != 1) return fail("%s: which = %d (0: training rows, 1: the attached matrix)", who, which);
+  if (which != 0 && which != 1 && which != 2) return fail("%s: which = %d (0: training rows, 1: the attached matrix, 2: the attached raw matrix)", who, which);
   if (which == 1 && !h->d_pred_rm) return fail("%s: no second matrix is attached (gpb_hip_hist_set_pred_bins)", who);
-  if (h->fpad > GPB_TP_MAX_FPAD) return fail("%s: rows of %d columns are wider than the %d bytes a staged row may take", who, h->F, GPB_TP_MAX_FPAD);
-  const int N = which == 0 ? h->n : h->n_pred;
+  const bool raw = which == 2;
+  if (raw) {
+    if (!h->d_pred_raw) return fail("%s: no raw matrix is attached (gpb_hip_hist_set_pred_raw)", who);
+    for (int t = tree_begin; t < tree_end; ++t)
+      if (!raw_has_rule(h, t)) return fail("%s: tree %d has no raw rule (gpb_hip_hist_forest_set_raw_rule)", who, t);
+  } else if (h->fpad > GPB_TP_MAX_FPAD) {
+    return fail("%s: rows of %d columns are wider than the %d bytes a staged row may take", who, h->F, GPB_TP_MAX_FPAD);
+  }
+  const int N = which == 0 ? h->n : raw ? h->n_raw : h->n_pred;
   if (!rows) cnt = N;
   if (cnt < 0) return fail("%s: cnt = %d", who, cnt);
   if (cnt == 0) return 0;
@@ -552,10 +641,12 @@ int tree_predict_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_be
     h->prows_pending = true;
     a.rows = h->d_prows; a.mult = with_mult ? h->d_prows + cnt : nullptr; a.cnt = m;
   }
-  int lds = 0, chunk = 0;                                  // the largest chunk of the range, by the rule of tree_predict_kernels.h
+  int lds = 0, chunk = 0;                                  // the largest chunk of the range, by the rule of tree_predict_kernels.h / tree_raw_kernels.h
   for (int t = tree_begin; t < tree_end; ++t) {
-    const int b = h->forest_desc[4 * (size_t)t + 2];
-    if (chunk > 0 && chunk + b > GPB_TP_CHUNK_BYTES) chunk = 0;
+    const int b = raw ? h->rawf_desc[4 * (size_t)t + 2] : h->forest_desc[4 * (size_t)t + 2];
+    if (chunk > 0 && chunk + b > (raw ? GPB_TR_CHUNK_BYTES : GPB_TP_CHUNK_BYTES)) chunk = 0;
+    // (raw forms are stored in the order their rules arrived: a chunk also ends where the next tree's form does not follow the previous one in the buffer)
+    if (raw && chunk > 0 && h->rawf_desc[4 * (size_t)t] != h->rawf_desc[4 * (size_t)t - 4] + h->rawf_desc[4 * (size_t)t - 2] / 4) chunk = 0;
     chunk += b; lds = std::max(lds, chunk);
   }
   a.lds_tree_bytes = lds;
@@ -563,13 +654,18 @@ int tree_predict_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_be
     if (h->pleaf_cap < cnt) { HIP_OK(hipStreamSynchronize(st)); dev_free(h->d_pleaf); h->pleaf_cap = 0; HIP_OK(hipMalloc(&h->d_pleaf, sizeof(int) * (size_t)cnt)); h->pleaf_cap = cnt; }
     a.leaf_out = h->d_pleaf;
   }
-  HIP_OK(gpb::launch_tree_predict(a, st));
+  gpb::TreeRawArgs ra;                                     // which = 2: the same call on the raw matrix and the raw forms (tree_raw_kernels.hip)
+  ra.x = h->d_pred_raw; ra.dtype = h->raw_dtype; ra.F = h->F; ra.row_stride = h->raw_stride; ra.rows = a.rows; ra.mult = a.mult; ra.cnt = a.cnt;
+  ra.forest = h->d_rawf; ra.desc = reinterpret_cast<const int4*>(h->d_rawf_desc); ra.tree_begin = tree_begin; ra.tree_end = tree_end;
+  ra.score = d_score; ra.leaf_out = a.leaf_out; ra.lds_tree_bytes = lds;
+  const auto launch = [&]() { return raw ? gpb::launch_tree_raw(ra, st) : gpb::launch_tree_predict(a, st); };
+  HIP_OK(launch());
   if (ms_avg) {      // measurement helper: the launch above was the warm-up; `reps` more of the same launch between two events
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
     const auto drop = scope_exit([&] { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); });
     HIP_OK(hipEventRecord(e0, st));
-    for (int rep = 0; rep < reps; ++rep) HIP_OK(gpb::launch_tree_predict(a, st));
+    for (int rep = 0; rep < reps; ++rep) HIP_OK(launch());
     HIP_OK(hipEventRecord(e1, st));
     HIP_OK(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -728,6 +824,7 @@ int tree_shap_impl(gpb_hip_hist_t* h, const char* who, int which, int tree_begin
   const int ntrees = (int)(h->forest_desc.size() / 4);
   if (tree_begin < 0 || tree_end > ntrees || tree_begin >= tree_end)
     return fail("%s: trees [%d, %d): the forest holds %d (unknown tree id or empty range)", who, tree_begin, tree_end, ntrees);
+  if (which == 2) return fail("%s: contributions need binned rows (which = 0 or 1): the path tables hold sets of bins", who);
   if (which != 0 && which != 1) return fail("%s: which = %d (0: training rows, 1: the attached matrix)", who, which);
   if (which == 1 && !h->d_pred_rm) return fail("%s: no second matrix is attached (gpb_hip_hist_set_pred_bins)", who);
   if (h->fpad > GPB_TP_MAX_FPAD) return fail("%s: rows of %d columns are wider than the %d bytes a staged row may take", who, h->F, GPB_TP_MAX_FPAD);
@@ -841,6 +938,62 @@ extern "C" int gpb_hip_hist_forest_clear(gpb_hip_hist_t* h) {
   HIP_OK(hipStreamSynchronize(h->stream));
   h->forest_words.clear(); h->forest_desc.clear();
   h->shap_words.clear(); h->shap_desc.clear(); h->shap_expected.clear();
+  h->rawf_words.clear(); h->rawf_desc.clear();
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_forest_set_raw_rule(gpb_hip_hist_t* h, int32_t tree_id, const double* threshold, const int8_t* decision_type, int32_t num_cat,
+                                                const int32_t* cat_boundaries, const uint32_t* cat_threshold) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (raw_set_rule(h, "gpb_hip_hist_forest_set_raw_rule", tree_id, threshold, decision_type, num_cat, cat_boundaries, cat_threshold)) return -1;
+  API_END();
+}
+
+namespace {
+
+// attach (copy of host rows, or a borrowed device pointer) or detach the raw matrix; the previous one is released first
+int set_pred_raw_impl(gpb_hip_hist_t* h, const char* who, int n_raw, int dtype, long long row_stride, const void* rows, bool on_device) {
+  const bool attach = rows && n_raw > 0;
+  const size_t eb = dtype == 0 ? 8 : 4;
+  if (attach) {                                            // refusals leave the matrix attached so far in place
+    if (dtype != 0 && dtype != 1) return fail("%s: dtype = %d (0: float64, 1: float32)", who, dtype);
+    if (row_stride < h->F) return fail("%s: row_stride = %lld elements, below the %d columns of the handle", who, row_stride, h->F);
+    if (h->F > (dtype == 0 ? GPB_TR_MAX_COLS_F64 : GPB_TR_MAX_COLS_F32))
+      return fail("%s: rows of %d %s columns are wider than the 64 staged rows of a workgroup allow: at most GPB_TR_MAX_COLS_F64 = %d float64 or "
+                  "GPB_TR_MAX_COLS_F32 = %d float32 columns", who, h->F, dtype == 0 ? "float64" : "float32", GPB_TR_MAX_COLS_F64, GPB_TR_MAX_COLS_F32);
+    if (on_device && (reinterpret_cast<uintptr_t>(rows) & (eb - 1))) return fail("%s: the device pointer is not aligned to its %d-byte elements", who, (int)eb);
+  }
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (h->pred_raw_owned) dev_free(h->d_pred_raw);
+  h->d_pred_raw = nullptr; h->pred_raw_owned = false; h->n_raw = 0;
+  if (!attach) return 0;
+  if (on_device) {
+    h->d_pred_raw = const_cast<void*>(rows);
+  } else {
+    const size_t bytes = ((size_t)(n_raw - 1) * (size_t)row_stride + (size_t)h->F) * eb;      // the last row ends with its last column
+    HIP_OK(hipMalloc(&h->d_pred_raw, bytes));
+    h->pred_raw_owned = true;
+    HIP_OK(hipMemcpy(h->d_pred_raw, rows, bytes, hipMemcpyHostToDevice));
+  }
+  h->n_raw = n_raw; h->raw_dtype = dtype; h->raw_stride = row_stride;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int gpb_hip_hist_set_pred_raw(gpb_hip_hist_t* h, int32_t n_raw, int32_t dtype, int64_t row_stride, const void* host_rows) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (set_pred_raw_impl(h, "gpb_hip_hist_set_pred_raw", n_raw, dtype, row_stride, host_rows, false)) return -1;
+  API_END();
+}
+
+extern "C" int gpb_hip_hist_set_pred_raw_dev(gpb_hip_hist_t* h, int32_t n_raw, int32_t dtype, int64_t row_stride, const void* dev_rows) {
+  API_BEGIN();
+  if (!h) return fail("null handle");
+  if (set_pred_raw_impl(h, "gpb_hip_hist_set_pred_raw_dev", n_raw, dtype, row_stride, dev_rows, true)) return -1;
   API_END();
 }
 
@@ -889,8 +1042,9 @@ extern "C" int gpb_hip_hist_add_score(gpb_hip_hist_t* h, int32_t which, int32_t 
   API_BEGIN();
   if (!h || !score) return fail("null argument");
   if (which == 1 && !h->d_pred_rm) return fail("gpb_hip_hist_add_score: no second matrix is attached (gpb_hip_hist_set_pred_bins)");
-  if (which != 0 && which != 1) return fail("gpb_hip_hist_add_score: which = %d (0: training rows, 1: the attached matrix)", which);
-  const int N = which == 0 ? h->n : h->n_pred;
+  if (which == 2 && !h->d_pred_raw) return fail("gpb_hip_hist_add_score: no raw matrix is attached (gpb_hip_hist_set_pred_raw)");
+  if (which != 0 && which != 1 && which != 2) return fail("gpb_hip_hist_add_score: which = %d (0: training rows, 1: the attached matrix, 2: the attached raw matrix)", which);
+  const int N = which == 0 ? h->n : which == 2 ? h->n_raw : h->n_pred;
   HIP_OK(hipSetDevice(h->device));
   if (h->pscore_cap < N) {
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -956,6 +1110,7 @@ extern "C" int gpb_hip_hist_add_contrib_bench(gpb_hip_hist_t* h, int32_t which, 
 extern "C" int gpb_hip_hist_add_contrib(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt, double* out) {
   API_BEGIN();
   if (!h || !out) return fail("null argument");
+  if (which == 2) return fail("gpb_hip_hist_add_contrib: contributions need binned rows (which = 0 or 1): the path tables hold sets of bins");
   if (which == 1 && !h->d_pred_rm) return fail("gpb_hip_hist_add_contrib: no second matrix is attached (gpb_hip_hist_set_pred_bins)");
   if (which != 0 && which != 1) return fail("gpb_hip_hist_add_contrib: which = %d (0: training rows, 1: the attached matrix)", which);
   const size_t len = (size_t)(which == 0 ? h->n : h->n_pred) * (size_t)(h->F + 1);

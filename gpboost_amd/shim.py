@@ -893,7 +893,55 @@ class HistBuilder(object):
                                                        C.c_double(shrinkage), C.byref(tid)))
         if k > 1 and tree.get("leaf_count") is not None:         # the cover counts the contributions need (the tree itself is stored either way)
             self.set_leaf_counts(tid.value, tree["leaf_count"])
+        if tree.get("threshold") is not None and tree.get("decision_type") is not None:      # the raw rule: scoring on feature values (pred="raw")
+            self.set_raw_rule(tid.value, tree["threshold"], tree["decision_type"], tree.get("cat_boundaries"), tree.get("cat_threshold"))
         return tid.value
+
+    def set_raw_rule(self, tree_id, threshold, decision_type, cat_boundaries=None, cat_threshold=None):
+        """The raw rule of a stored tree, one entry per node as the reference's Tree keeps it: real-valued threshold (a categorical node: its index into
+        cat_boundaries), decision_type (bit 0 categorical, bit 1 default-left, bits 2-3 missing type None / Zero / NaN), the bitsets over category values.
+        With it the tree scores rows of feature values (pred="raw") next to binned ones."""
+        thr = np.ascontiguousarray(threshold, dtype=np.float64)
+        dt = np.ascontiguousarray(decision_type, dtype=np.int8)
+        if thr.size != dt.size:
+            raise ValueError("threshold and decision_type must have one entry per node")
+        cb = None if cat_boundaries is None else np.ascontiguousarray(cat_boundaries, dtype=np.int32)
+        ct = None if cat_threshold is None else np.ascontiguousarray(cat_threshold, dtype=np.uint32)
+        num_cat = 0 if cb is None else cb.size - 1
+        if num_cat > 0 and (ct is None or (np.all(np.diff(cb) > 0) and cb[0] >= 0 and ct.size < cb[-1])):
+            raise ValueError("cat_threshold must hold the cat_boundaries[-1] words of the bitsets")
+        _shim_call(_lib().gpb_hip_hist_forest_set_raw_rule(self.h, C.c_int(int(tree_id)), _p(thr), _p(dt, C.c_int8), C.c_int(max(num_cat, 0)), _p(cb, C.c_int),
+                                                           _p(ct, C.c_uint32)))
+
+    @staticmethod
+    def raw_rule_from_bins(tree, bin_upper_bound, missing_type, bin_to_category=None):
+        """The raw rule (the keyword arguments of set_raw_rule) of a tree grown on bins, from the mappers that made the bins.  bin_upper_bound[f]: the upper
+        bounds of column f's bins (a numerical node sends x <= bin_upper_bound[f][threshold_in_bin] left); missing_type[f]: 0 None / 1 Zero / 2 NaN;
+        bin_to_category[f]: the category value of every bin of a categorical column (a categorical node's set of bins becomes a bitset over those values).
+        Host only: needs no handle and no device."""
+        nn = int(tree["num_leaves"]) - 1
+        sf = np.asarray(tree["split_feature_inner"])[:nn]
+        is_cat = np.zeros(nn, dtype=bool) if tree.get("node_is_cat") is None else np.asarray(tree["node_is_cat"])[:nn] != 0
+        thr = np.zeros(nn); dt = np.zeros(nn, dtype=np.int8)
+        bounds, words = [0], []
+        for i in range(nn):
+            f = int(sf[i])
+            mt = int(missing_type[f]) << 2
+            if not is_cat[i]:
+                thr[i] = bin_upper_bound[f][int(tree["threshold_in_bin"][i])]
+                dt[i] = (2 if tree["default_left"][i] else 0) | mt
+                continue
+            bits = np.asarray(tree["node_cat_bits"], dtype=np.uint32).reshape(-1, 8)[i]
+            cats = [int(bin_to_category[f][b]) for b in range(min(256, len(bin_to_category[f]))) if (int(bits[b >> 5]) >> (b & 31)) & 1]
+            if any(c < 0 for c in cats):
+                raise ValueError("category values are non-negative integers")
+            w = np.zeros(max(cats) // 32 + 1 if cats else 1, dtype=np.uint32)
+            for c in cats:
+                w[c >> 5] |= np.uint32(1 << (c & 31))
+            thr[i] = len(bounds) - 1; dt[i] = 1 | mt
+            words.append(w); bounds.append(bounds[-1] + w.size)
+        return dict(threshold=thr, decision_type=dt, cat_boundaries=np.array(bounds, dtype=np.int32),
+                    cat_threshold=np.concatenate(words) if words else np.zeros(0, dtype=np.uint32))
 
     def keep_last_tree(self, shrinkage=1.0):
         """Stores the last tree grow_tree has grown on this handle -> its id."""
@@ -921,18 +969,47 @@ class HistBuilder(object):
         _shim_call(_lib().gpb_hip_hist_set_pred_bins(self.h, C.c_int(b.shape[1]), _p(b, C.c_uint8)))
         self.n_pred = b.shape[1]
 
+    def set_pred_raw(self, X=None):
+        """Attaches a matrix of feature VALUES, (n_raw, F) float64 or float32, C-contiguous, copied to the device as it is (no binning); None detaches.
+        The scoring calls reach it with pred="raw"; the trees they apply need a raw rule (set_raw_rule)."""
+        if X is None:
+            _shim_call(_lib().gpb_hip_hist_set_pred_raw(self.h, C.c_int(0), C.c_int(0), C.c_int64(0), None))
+            self.n_raw = 0
+            return
+        if not (isinstance(X, np.ndarray) and X.ndim == 2 and X.dtype in (np.float64, np.float32) and X.flags.c_contiguous and X.shape[1] == self.F):
+            raise ValueError("X must be a C-contiguous (n_raw, F = %d) float64 or float32 array" % self.F)
+        _shim_call(_lib().gpb_hip_hist_set_pred_raw(self.h, C.c_int(X.shape[0]), C.c_int(0 if X.dtype == np.float64 else 1), C.c_int64(self.F),
+                                                    C.c_void_p(X.ctypes.data)))
+        self.n_raw = X.shape[0]
+
+    def set_pred_raw_dev(self, ptr, n, dtype, row_stride=None):
+        """set_pred_raw on a device pointer (e.g. a torch tensor's data_ptr()): n rows of F columns of dtype float64 / float32, row_stride elements apart
+        (None: F).  Nothing is copied: the memory must stay valid while it is attached."""
+        dt = np.dtype(dtype)
+        if dt not in (np.float64, np.float32):
+            raise ValueError("dtype must be float64 or float32")
+        _shim_call(_lib().gpb_hip_hist_set_pred_raw_dev(self.h, C.c_int(int(n)), C.c_int(0 if dt == np.float64 else 1),
+                                                        C.c_int64(self.F if row_stride is None else int(row_stride)), C.c_void_p(int(ptr))))
+        self.n_raw = int(n)
+
+    @staticmethod
+    def _which(pred):
+        """The matrix selector of the scoring entry points: False the training bins, True the attached bins, "raw" the attached feature values."""
+        return 2 if isinstance(pred, str) and pred == "raw" else int(bool(pred))
+
     def _score_rows(self, rows, pred):
-        n = getattr(self, "n_pred", 0) if pred else self.n
+        n = (getattr(self, "n_raw", 0) if self._which(pred) == 2 else getattr(self, "n_pred", 0)) if pred else self.n
         r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
         return n, r, (n if r is None else r.size)
 
     def predict_leaf(self, tree_id, rows=None, pred=False):
-        """-> leaf of every listed row (None: all rows) of the training matrix or, pred=True, of the attached one in the stored tree tree_id."""
+        """-> leaf of every listed row (None: all rows) of the training matrix or, pred=True, of the attached one (pred="raw": of the attached matrix of feature
+        values) in the stored tree tree_id."""
         n, r, cnt = self._score_rows(rows, pred)
         out = np.empty(cnt, dtype=np.int32)
         if r is not None and cnt == 0:
             return out
-        _shim_call(_lib().gpb_hip_hist_predict_leaf(self.h, C.c_int(int(bool(pred))), C.c_int(int(tree_id)), _p(r, C.c_int), C.c_int(cnt), _p(out, C.c_int)))
+        _shim_call(_lib().gpb_hip_hist_predict_leaf(self.h, C.c_int(self._which(pred)), C.c_int(int(tree_id)), _p(r, C.c_int), C.c_int(cnt), _p(out, C.c_int)))
         return out
 
     def _tree_range(self, trees):
@@ -953,7 +1030,7 @@ class HistBuilder(object):
         t0, t1 = self._tree_range(trees)
         if r is not None and cnt == 0:
             return score
-        _shim_call(_lib().gpb_hip_hist_add_score(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(score)))
+        _shim_call(_lib().gpb_hip_hist_add_score(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(score)))
         return score
 
     def add_score_dev(self, score_dev_ptr, trees=None, rows=None, pred=False):
@@ -963,7 +1040,7 @@ class HistBuilder(object):
         t0, t1 = self._tree_range(trees)
         if r is not None and cnt == 0:
             return
-        _shim_call(_lib().gpb_hip_hist_add_score_dev(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+        _shim_call(_lib().gpb_hip_hist_add_score_dev(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
                                                      C.c_void_p(int(score_dev_ptr))))
 
     def add_score_bench(self, score_dev_ptr, trees=None, rows=None, pred=False, reps=20):
@@ -971,7 +1048,7 @@ class HistBuilder(object):
         n, r, cnt = self._score_rows(rows, pred)
         t0, t1 = self._tree_range(trees)
         ms = C.c_double(0)
-        _shim_call(_lib().gpb_hip_hist_add_score_bench(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+        _shim_call(_lib().gpb_hip_hist_add_score_bench(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
                                                        C.c_void_p(int(score_dev_ptr)), C.c_int(int(reps)), C.byref(ms)))
         return ms.value
 
@@ -1018,7 +1095,7 @@ class HistBuilder(object):
         t0, t1 = self._tree_range(trees)
         if r is not None and cnt == 0:
             return out
-        _shim_call(_lib().gpb_hip_hist_add_contrib(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(out)))
+        _shim_call(_lib().gpb_hip_hist_add_contrib(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt), _p(out)))
         return out
 
     def add_contrib_dev(self, out_dev_ptr, trees=None, rows=None, pred=False):
@@ -1028,7 +1105,7 @@ class HistBuilder(object):
         t0, t1 = self._tree_range(trees)
         if r is not None and cnt == 0:
             return
-        _shim_call(_lib().gpb_hip_hist_add_contrib_dev(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+        _shim_call(_lib().gpb_hip_hist_add_contrib_dev(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
                                                        C.c_void_p(int(out_dev_ptr))))
 
     def add_contrib_bench(self, out_dev_ptr, trees=None, rows=None, pred=False, reps=20):
@@ -1036,7 +1113,7 @@ class HistBuilder(object):
         n, r, cnt = self._score_rows(rows, pred)
         t0, t1 = self._tree_range(trees)
         ms = C.c_double(0)
-        _shim_call(_lib().gpb_hip_hist_add_contrib_bench(self.h, C.c_int(int(bool(pred))), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
+        _shim_call(_lib().gpb_hip_hist_add_contrib_bench(self.h, C.c_int(self._which(pred)), C.c_int(t0), C.c_int(t1), _p(r, C.c_int), C.c_int(cnt),
                                                          C.c_void_p(int(out_dev_ptr)), C.c_int(int(reps)), C.byref(ms)))
         return ms.value
 

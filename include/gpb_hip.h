@@ -792,7 +792,7 @@ GPB_HIP_EXPORT int gpb_hip_hist_find_best_split(gpb_hip_hist_t* h, int32_t slot,
  *   forest_size / forest_clear   number of stored trees / drop them all (ids start at 0 again)
  *   set_pred_bins       attaches a second matrix: F x n_pred uint8, feature-major, binned with the SAME mappers as the training data (what a validation
  *                       Dataset aligned with the training Dataset holds); NULL or n_pred <= 0 detaches
- *   predict_leaf        leaf_out[i] = leaf of rows[i] in tree tree_id; which: 0 the training rows, 1 the attached matrix; rows == NULL: all rows (cnt ignored)
+ *   predict_leaf        leaf_out[i] = leaf of rows[i] in tree tree_id; which: 0 the training rows, 1 the attached matrix (2: the raw one, below); rows == NULL: all rows (cnt ignored)
  *   add_score           score: HOST array over ALL rows of the matrix; score[rows[i]] += value_t[leaf_t(rows[i])] for t = tree_begin .. tree_end - 1, strictly
  *                       in tree order, once per OCCURRENCE in rows, without fused multiply-adds: bit-identical to the host loop
  *                       for t: for i: score[rows[i]] += value_t[leaf_t[rows[i]]]  (Tree::AddPredictionToScore(data, data_indices, cnt, score)), and independent
@@ -822,6 +822,26 @@ GPB_HIP_EXPORT int gpb_hip_hist_sync(gpb_hip_hist_t* h);
  * handle's stream; *ms_avg = their mean.  The scores end up with reps + 1 updates. */
 GPB_HIP_EXPORT int gpb_hip_hist_add_score_bench(gpb_hip_hist_t* h, int32_t which, int32_t tree_begin, int32_t tree_end, const int32_t* rows, int32_t cnt,
                                                 double* score_dev, int32_t reps, double* ms_avg);
+
+/* Scoring on RAW feature rows (tree_raw_kernels.hip): which = 2 in predict_leaf / add_score / add_score_dev / add_score_bench selects a row-major matrix of feature
+ * VALUES, float64 or float32, that was never binned; the walk is Tree::Decision (include/LightGBM/tree.h:329-401) per node.  Tree ranges, row lists and the order
+ * of the additions are those of the binned calls; the leaf values are the same stored doubles, so the scores agree bit for bit wherever the leaves agree.
+ *   forest_set_raw_rule  the raw rule of the stored tree tree_id, one entry per node, as the reference's Tree keeps it: threshold (real-valued; of a categorical
+ *                        node its index into cat_boundaries), decision_type (bit 0 categorical, bit 1 default-left, bits 2-3 the missing type 0 None / 1 Zero /
+ *                        2 NaN), and for categorical nodes cat_boundaries (num_cat + 1 ascending word offsets) / cat_threshold (bitsets over category VALUES).
+ *                        Columns, children and leaf values are those of the stored tree.  Refused, with nothing stored: an unknown tree id, the missing type 3,
+ *                        a categorical index outside num_cat, boundaries not ascending, a non-finite numerical threshold, a raw form beyond the 12288 bytes a
+ *                        chunk of trees may take in LDS (32 bytes per node, 8 per leaf, 4 per bitset word).  A tree without a rule stays usable for bins.
+ *   set_pred_raw         copies n_raw rows of F columns from the host: dtype 0 float64, 1 float32; row_stride in elements, >= F; NULL or n_raw <= 0 detaches
+ *   set_pred_raw_dev     borrows a DEVICE pointer of the same layout (no copy; it must stay valid while attached); replaces / is replaced by set_pred_raw
+ * A categorical value outside [-2^31, 2^31) goes right (the reference's conversion to int is undefined there); NaN goes right under the missing type NaN and counts
+ * as category 0 otherwise.  Refusals in the scoring calls, before any launch: no raw matrix attached, "tree K has no raw rule", rows outside the raw matrix;
+ * when attaching: more than 103 float64 / 207 float32 columns (GPB_TR_MAX_COLS_F64 / _F32: 64 staged rows must fit a launch).  Contributions (add_contrib*) with
+ * which = 2 are refused: "contributions need binned rows". */
+GPB_HIP_EXPORT int gpb_hip_hist_forest_set_raw_rule(gpb_hip_hist_t* h, int32_t tree_id, const double* threshold, const int8_t* decision_type, int32_t num_cat,
+                                                    const int32_t* cat_boundaries, const uint32_t* cat_threshold);
+GPB_HIP_EXPORT int gpb_hip_hist_set_pred_raw(gpb_hip_hist_t* h, int32_t n_raw, int32_t dtype, int64_t row_stride, const void* host_rows);
+GPB_HIP_EXPORT int gpb_hip_hist_set_pred_raw_dev(gpb_hip_hist_t* h, int32_t n_raw, int32_t dtype, int64_t row_stride, const void* dev_rows);
 
 /* Per-feature contributions (TreeSHAP) of stored trees on the device: out[row][f] += phi_f of every tree of the range, out[row][F] += the trees' expected values
  * -- the matrix of the reference's predict(..., pred_contrib=True) for one class, on BINNED rows.  Stands in for Tree::PredictContrib -> the recursive
